@@ -9,6 +9,7 @@ vector [1,2816]); inputs are resident in HBM before the timed region.  One proce
 sharded one per rank (weak scaling), weights are broadcast once from rank 0 over RCCL, no collective inside a sample.
 
     python bench.py --gpus 1 --steps 2 --warmup 1
+    python bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs DIR     # + DIR/samples.npy: the last timed step's images
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 ...
 """
 import argparse
@@ -479,6 +480,29 @@ class StdoutForTheLine:
         return False
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6      # --dump-outputs: the .npy files of one run together stay under this
+
+
+def dump_outputs(arrays, out_dir, max_bytes=DUMP_MAX_BYTES):
+    """{name: tensor} -> out_dir/<name>.npy in float32, for comparing two builds output for output.  Arrays that together exceed
+    `max_bytes` are each cut to a fixed, seeded sample of their flattened elements (the indices depend only on the element count, so
+    every run with the same arguments samples the same positions).  Returns {name: path}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(t.numel() for t in arrays.values())
+    cap = (max_bytes - 1024 * len(arrays)) // 4          # float32 elements in all, less room for the .npy headers
+    paths = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        if total > cap:
+            keep = t.numel() * cap // total
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            a = a.reshape(-1)[idx]
+        paths[name] = os.path.join(out_dir, name + ".npy")
+        np.save(paths[name], a.numpy())
+    return paths
+
+
 def _fused_step_on():
     from supir_amd.modules import sampling
     return bool(sampling.FUSED_EDM_STEP)
@@ -515,7 +539,14 @@ def main():
     ap.add_argument("--no-replay-profile", action="store_true",
                     help="skip the same-box sub-step that re-runs this command (1 image) under rocprofv3 --kernel-trace --stats for the "
                          "dominant kernel's average duration under graph replay (roofline.frac_graph_replay)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned (the images of batchify_sample) as DIR/samples.npy, "
+                         "float32 (DIR/samples_rank<r>.npy per rank on several GPUs), at most 64 MB in all: a fixed, seeded sample "
+                         "of the elements when larger.  Compare builds with --tune file: the default --tune box picks kernels by "
+                         "timing, and a different pick moves the images at bf16 rounding level")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     the_line = StdoutForTheLine()
 
@@ -622,6 +653,8 @@ def main():
     dt_rank = time.perf_counter() - t0          # this rank's own clock, before the closing barrier
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:   # outside the timed region, before anything else runs on the model
+        dump_outputs({"samples" if world == 1 else f"samples_rank{rank}": out}, args.dump_outputs, DUMP_MAX_BYTES // world)
     if args.rank_report:
         # one line per rank on stderr (tools/scale_dryrun.sh collects them): start-up and steady-state figures of THIS rank
         try:

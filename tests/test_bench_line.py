@@ -96,3 +96,23 @@ def test_replay_profile_kernel_names_match_the_kernels_template_arity():
         assert want is not None
         if norm:
             assert any(want in s for s in norm), (trace_name, want)
+
+
+def test_dump_outputs_writes_float32_and_samples_under_the_cap(tmp_path):
+    """--dump-outputs: small outputs land whole as float32; larger ones become the same seeded sample on every run, under the cap."""
+    import numpy as np
+    import torch
+    small = torch.linspace(-1, 1, 3 * 8 * 8, dtype=torch.bfloat16).reshape(1, 3, 8, 8)
+    p = bench.dump_outputs({"samples": small}, str(tmp_path / "a"))
+    got = np.load(p["samples"])
+    assert got.dtype == np.float32 and got.shape == (1, 3, 8, 8) and np.array_equal(got, small.float().numpy())
+
+    big = {"x": torch.randn(2, 3, 64, 64, generator=torch.Generator().manual_seed(1)), "y": torch.randn(5000, dtype=torch.float64)}
+    cap = 40_000
+    p1 = bench.dump_outputs(big, str(tmp_path / "b"), max_bytes=cap)
+    p2 = bench.dump_outputs(big, str(tmp_path / "c"), max_bytes=cap)
+    assert sum(os.path.getsize(f) for f in p1.values()) <= cap
+    for name, t in big.items():
+        a, b = np.load(p1[name]), np.load(p2[name])
+        assert a.dtype == np.float32 and a.ndim == 1 and 0 < a.size < t.numel() and np.array_equal(a, b)
+        assert np.isin(a, t.float().reshape(-1).numpy()).all()

@@ -277,7 +277,7 @@ def test_bigg_tower_vs_transformers_cliptextmodelwithprojection():
     (pre-LN residual block, packed-QKV multi-head attention with the causal mask, erf-GELU MLP) that the stand-in restates, and with it the
     oracle's and the product's towers, which the other tests hold to these fixtures."""
     from transformers import CLIPTextConfig, CLIPTextModelWithProjection
-    gold = torch.load("tests/golden/golden_cond.pt")
+    gold = _cond_golden()
     D, LAYERS, HEADS, PROJ, L_WIDTH = 320, 6, 20, 320, 192          # oracle/gen_golden_cond.py: the reduced "bigG" of the fixtures
     cfg = CLIPTextConfig(vocab_size=49408, hidden_size=D, intermediate_size=4 * D, num_hidden_layers=LAYERS, num_attention_heads=HEADS,
                          max_position_embeddings=77, hidden_act="gelu", projection_dim=PROJ, eos_token_id=2)   # 2: pooled row = argmax(ids)
