@@ -337,6 +337,29 @@ int supir_edm_step_pre_tiles(const float* x, const float* eps, float s_noise, fl
 int supir_tile_blend(const float* tiles, const double* weights, float* canvas, const int* tile_hw, int k, int b, int C, int Hc, int Wc,
                      int T, void* stream);
 
+/* The post half of ONE DPM-Solver++(2M) SDE step on fp32 latents (RestoreDPMPP2MSampler.sampler_step,
+ * sgm/modules/diffusionmodules/sampling.py:429-483, over DPMPP2MSampler.get_variables / get_mult :291-330, with LinearCFG
+ * guiders.py:44-74 and the EpsScaling denoiser wrapper denoiser.py:66-73 + denoiser_scaling.py:16-22).  The pre half is
+ * supir_edm_step_pre[_tiles] with eps = NULL (x * c_in for every CFG copy).  m1..m4 and noise_mul are host scalars (fp32, the
+ * reference's operation order): m1 = exp(-t_next) / exp(-t) * exp(-eta h), m2 = expm1(-h - eta h), m3 = 1 + 1 / (2 r), m4 = 1 / (2 r),
+ * noise_mul = sigma_next * sqrt(-expm1(-2 eta h)).  reps as for the EDM step.
+ *   den_r = net_out[r*n + i] * c_out + x[i] * c_skip;  den = den_0 + cfg_scale * (den_1 - den_0) (reps 2) | den_0;  den_out[i] = den
+ *   old NULL (first / last step, :463-464):  x_next[i] = m1 * x[i] - m2 * den
+ *   otherwise (:466-482):  dd = m3 * den - m4 * old[i];  x_next[i] = m1 * x[i] - m2 * dd
+ *                          eps != NULL: x_next[i] = x_next[i] + (eps[i] * noise_mul) * s_noise
+ * Every product and sum is rounded separately (no fused multiply-add), as the torch expressions are.
+ *   supir_dpmpp2m_step_post: the whole batch, n elements per copy; all pointers 16-byte aligned, n % 4 == 0 when reps == 2.
+ *   supir_dpmpp2m_step_post_tiles: net_out [reps][k*b][C][T][T] and x [k*b][C][T][T] are the stacked tiles of
+ *       supir_edm_step_pre_tiles; old / eps (either may be NULL) are CANVASES [b][C][Hc][Wc] read through the k tile windows tile_hw
+ *       (TiledRestoreDPMPP2MSampler, sampling.py:663-730); x_next / den_out are written stacked.  k <= 64, windows inside the
+ *       canvas, b * C <= 65535.  Blend the results with supir_tile_blend. */
+int supir_dpmpp2m_step_post(const float* net_out, const float* x, const float* old, const float* eps, float c_out, float c_skip,
+                            float cfg_scale, float m1, float m2, float m3, float m4, float noise_mul, float s_noise, float* x_next,
+                            float* den_out, long n, int reps, void* stream);
+int supir_dpmpp2m_step_post_tiles(const float* net_out, const float* x, const float* old, const float* eps, float c_out, float c_skip,
+                                  float cfg_scale, float m1, float m2, float m3, float m4, float noise_mul, float s_noise, float* x_next,
+                                  float* den_out, const int* tile_hw, int k, int b, int C, int Hc, int Wc, int T, int reps, void* stream);
+
 /* Touch one dword per 128-byte line of [p, p+bytes) (a weight matrix) so that it is in flight through the memory-side
  * cache before the kernel that consumes it starts; launched a few ops ahead on a separate stream. `sink`: any 4 writable
  * device bytes (never written in practice). No reference counterpart: the reference re-reads fp32 weights through

@@ -50,6 +50,10 @@ SIGNATURES = {
     "supir_edm_step_pre_tiles": [P, P, F, F, F, P, P, P, I, I, I, I, I, I, I, P],
     # tiles, weights (fp64 [T][T]), canvas, tile_hw, k, b, C, Hc, Wc, T, stream
     "supir_tile_blend": [P, P, P, P, I, I, I, I, I, I, P],
+    # net_out, x, old, eps, c_out, c_skip, cfg_scale, m1, m2, m3, m4, noise_mul, s_noise, x_next, den_out, n, reps, stream
+    "supir_dpmpp2m_step_post": [P, P, P, P, F, F, F, F, F, F, F, F, F, P, P, L, I, P],
+    # ... x_next, den_out, tile_hw (host int[2k]), k, b, C, Hc, Wc, T, reps, stream
+    "supir_dpmpp2m_step_post_tiles": [P, P, P, P, F, F, F, F, F, F, F, F, F, P, P, P, I, I, I, I, I, I, I, P],
     "supir_gemm_tile_for": [I, I, I],
     "supir_prefetch": [P, c_size_t, P, P],
     "supir_groupnorm_nhwc_parts": [P, P, P, P, I, I, I, I, I, I, P, P, F, I, P, P, I, F, P, I, P, I, P, I, P],

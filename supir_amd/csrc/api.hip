@@ -395,6 +395,24 @@ int supir_tile_blend(const float* tiles, const double* weights, float* canvas, c
     return supir_tile_blend_launch(tiles, weights, canvas, tl, b, C, Hc, Wc, T, (hipStream_t)stream);
 }
 
+int supir_dpmpp2m_step_post(const float* net_out, const float* x, const float* old, const float* eps, float c_out, float c_skip,
+                            float cfg_scale, float m1, float m2, float m3, float m4, float noise_mul, float s_noise, float* x_next,
+                            float* den_out, long n, int reps, void* stream) {
+    if (!net_out || !x || !x_next || !den_out) return SUPIR_ERR_ARG;   // old NULL: first / last step; eps NULL: no noise
+    return supir_dpmpp2m_post_launch(net_out, x, old, eps, c_out, c_skip, cfg_scale, m1, m2, m3, m4, noise_mul, s_noise, x_next, den_out, n,
+                                     reps, (hipStream_t)stream);
+}
+
+int supir_dpmpp2m_step_post_tiles(const float* net_out, const float* x, const float* old, const float* eps, float c_out, float c_skip,
+                                  float cfg_scale, float m1, float m2, float m3, float m4, float noise_mul, float s_noise, float* x_next,
+                                  float* den_out, const int* tile_hw, int k, int b, int C, int Hc, int Wc, int T, int reps, void* stream) {
+    if (!net_out || !x || !x_next || !den_out) return SUPIR_ERR_ARG;
+    SupirTileList tl;
+    if (const int rc = pack_tiles(tl, tile_hw, k)) return rc;
+    return supir_dpmpp2m_post_tiles_launch(net_out, x, old, eps, c_out, c_skip, cfg_scale, m1, m2, m3, m4, noise_mul, s_noise, x_next, den_out,
+                                           tl, b, C, Hc, Wc, T, reps, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------------------------------------------- grouped launches
 static void pack_common(GemmArgs& a, const supir_gemm_shape& sh, const supir_gemm_problem& q) {
     a.A = (const bf16_t*)q.A; a.Wt = (const bf16_t*)q.W; a.C = q.C; a.C2 = q.C2;

@@ -190,6 +190,13 @@ int supir_edm_pre_tiles_launch(const float* x, const float* eps, float s_noise, 
                                const SupirTileList& tl, int b, int C, int Hc, int Wc, int T, int reps, hipStream_t st);
 int supir_tile_blend_launch(const float* tiles, const double* w, float* canvas, const SupirTileList& tl, int b, int C, int Hc, int Wc, int T,
                             hipStream_t st);
+// sampler.hip: the post half of one DPM++(2M) step -- whole batch, and stacked tiles reading old / eps through the tile windows
+int supir_dpmpp2m_post_launch(const float* net_out, const float* x, const float* old, const float* eps, float c_out, float c_skip, float cfg,
+                              float m1, float m2, float m3, float m4, float noise_mul, float s_noise, float* x_next, float* den_out, long n,
+                              int reps, hipStream_t st);
+int supir_dpmpp2m_post_tiles_launch(const float* net_out, const float* x, const float* old, const float* eps, float c_out, float c_skip,
+                                    float cfg, float m1, float m2, float m3, float m4, float noise_mul, float s_noise, float* x_next,
+                                    float* den_out, const SupirTileList& tl, int b, int C, int Hc, int Wc, int T, int reps, hipStream_t st);
 int supir_prefetch_launch(const void* p, size_t bytes, void* sink, hipStream_t st);
 int supir_resample_u8_launch(const uint8_t* src, uint8_t* dst_u8, float* dst_f32, const float* lut, const int* bounds, const int* kk,
                              int ksize, int in_h, int in_w, int out_h, int out_w, int ch, int vertical, hipStream_t st);

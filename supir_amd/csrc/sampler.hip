@@ -25,6 +25,15 @@
 //               bitwise the k sequential slice-adds.  The reference's weights are float64 (gaussian_weights builds them with
 //               numpy, sampling.py:733-750), so torch evaluates `fp32 += fp32 * fp64` in float64 and rounds to fp32 once per add:
 //               (float)((double)acc + (double)out * w), mul and add rounded separately (no fma) -- reproduced here.
+//
+// DPM-Solver++(2M) SDE (RestoreDPMPP2MSampler.sampler_step, sampling.py:429-483, in the port's operation order): the pre half is
+// `pre` / `pre_tiles` with eps == NULL (no churn before the call); the post half takes m1..m4 and noise_mul (get_variables /
+// get_mult, evaluated on the host in fp32) as scalars:
+//   dpmpp_post: den_r = net_out[r] * c_out + x * c_skip;  den = den_0 + cfg * (den_1 - den_0) (reps == 2) | den_0;  den_out = den
+//               old == NULL (first / last step): x_next = m1 * x - m2 * den
+//               otherwise: dd = m3 * den - m4 * old;  x_next = m1 * x - m2 * dd;  eps != NULL: x_next = x_next + (eps * noise_mul) * s_noise
+//   dpmpp_post_tiles: the same on the stacked tiles of pre_tiles, reading old / eps (canvases) through the k tile windows.
+// These two round every product and sum separately (no fma contraction), as the torch expressions they replace do.
 #include "kernels.h"
 
 namespace {
@@ -132,6 +141,71 @@ __global__ __launch_bounds__(256) void tile_blend_kernel(const float* __restrict
     if (any) *dst = acc;
 }
 
+__device__ __forceinline__ void dpmpp_post_one(float n0, float n1, float x, float old, float eps, bool has_old, bool has_eps, int reps,
+                                               float c_out, float c_skip, float cfg, float m1, float m2, float m3, float m4,
+                                               float noise_mul, float s_noise, float& x_next, float& den_out) {
+#pragma clang fp contract(off)
+    float den = n0 * c_out + x * c_skip;
+    if (reps == 2) {
+        const float den1 = n1 * c_out + x * c_skip;
+        den = den + cfg * (den1 - den);
+    }
+    den_out = den;
+    if (!has_old) {
+        x_next = m1 * x - m2 * den;
+        return;
+    }
+    const float dd = m3 * den - m4 * old;
+    float xn = m1 * x - m2 * dd;
+    if (has_eps) xn = xn + (eps * noise_mul) * s_noise;
+    x_next = xn;
+}
+
+__global__ __launch_bounds__(256) void dpmpp_post_kernel(const float* __restrict__ net_out, const float* __restrict__ x,
+                                                          const float* __restrict__ old, const float* __restrict__ eps, float c_out,
+                                                          float c_skip, float cfg, float m1, float m2, float m3, float m4, float noise_mul,
+                                                          float s_noise, float* __restrict__ x_next, float* __restrict__ den_out, long n,
+                                                          int reps) {
+    const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    const bool ho = old != nullptr, he = ho && eps != nullptr;
+    if (i + 4 <= n) {
+        const f32x4 n0 = *(const f32x4*)(net_out + i);
+        const f32x4 n1 = reps == 2 ? *(const f32x4*)(net_out + n + i) : n0;
+        const f32x4 xv = *(const f32x4*)(x + i);
+        const f32x4 ov = ho ? *(const f32x4*)(old + i) : xv;
+        const f32x4 ev = he ? *(const f32x4*)(eps + i) : xv;
+        float o[4], d[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            dpmpp_post_one(n0[k], n1[k], xv[k], ov[k], ev[k], ho, he, reps, c_out, c_skip, cfg, m1, m2, m3, m4, noise_mul, s_noise, o[k], d[k]);
+        *(f32x4*)(x_next + i) = f32x4{o[0], o[1], o[2], o[3]};
+        *(f32x4*)(den_out + i) = f32x4{d[0], d[1], d[2], d[3]};
+    } else {
+        for (long j = i; j < n; ++j)
+            dpmpp_post_one(net_out[j], reps == 2 ? net_out[n + j] : 0.f, x[j], ho ? old[j] : 0.f, he ? eps[j] : 0.f, ho, he, reps, c_out,
+                           c_skip, cfg, m1, m2, m3, m4, noise_mul, s_noise, x_next[j], den_out[j]);
+    }
+}
+
+__global__ __launch_bounds__(256) void dpmpp_post_tiles_kernel(const float* __restrict__ net_out, const float* __restrict__ x,
+                                                                const float* __restrict__ old, const float* __restrict__ eps, float c_out,
+                                                                float c_skip, float cfg, float m1, float m2, float m3, float m4,
+                                                                float noise_mul, float s_noise, float* __restrict__ x_next,
+                                                                float* __restrict__ den_out, SupirTileList tl, int b, int C, int Hc,
+                                                                int Wc, int T, int reps) {
+    const int idx = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (idx >= T * T) return;
+    const int y = idx / T, xx = idx - y * T;
+    const int bc = (int)blockIdx.y, j = (int)blockIdx.z;   // (sample, channel) plane; tile
+    const long src = ((long)bc * Hc + tl.hi[j] + y) * Wc + tl.wi[j] + xx;
+    const long dst = (((long)j * b * C + bc) * T + y) * T + xx;
+    const long n = (long)tl.n * b * C * T * T;
+    const bool ho = old != nullptr, he = ho && eps != nullptr;
+    dpmpp_post_one(net_out[dst], reps == 2 ? net_out[n + dst] : 0.f, x[dst], ho ? old[src] : 0.f, he ? eps[src] : 0.f, ho, he, reps, c_out,
+                   c_skip, cfg, m1, m2, m3, m4, noise_mul, s_noise, x_next[dst], den_out[dst]);
+}
+
 }  // namespace
 
 int supir_edm_pre_tiles_launch(const float* x, const float* eps, float s_noise, float noise_mul, float c_in, float* x_hat, float* net_in,
@@ -182,5 +256,31 @@ int supir_edm_post_launch(const float* net_out, const float* x_hat, const float*
     if (nb > 0x7fffffffL) return SUPIR_ERR_SHAPE;
     SUPIR_LAUNCH(edm_post_kernel, dim3((unsigned)nb), dim3(256), 0, st, net_out, x_hat, x_center, c_out, c_skip, cfg, restore_mul,
                  sigma_hat, dt, x_next, n, reps);
+    return SUPIR_LAUNCH_STATUS();
+}
+
+int supir_dpmpp2m_post_launch(const float* net_out, const float* x, const float* old, const float* eps, float c_out, float c_skip, float cfg,
+                              float m1, float m2, float m3, float m4, float noise_mul, float s_noise, float* x_next, float* den_out, long n,
+                              int reps, hipStream_t st) {
+    if (n <= 0 || reps < 1 || reps > 2) return SUPIR_ERR_ARG;
+    if (((uintptr_t)net_out | (uintptr_t)x | (uintptr_t)old | (uintptr_t)eps | (uintptr_t)x_next | (uintptr_t)den_out) & 15 ||
+        (reps == 2 && (n & 3)))
+        return SUPIR_ERR_SHAPE;
+    const long nb = (n + 1023) / 1024;
+    if (nb > 0x7fffffffL) return SUPIR_ERR_SHAPE;
+    SUPIR_LAUNCH(dpmpp_post_kernel, dim3((unsigned)nb), dim3(256), 0, st, net_out, x, old, eps, c_out, c_skip, cfg, m1, m2, m3, m4, noise_mul,
+                 s_noise, x_next, den_out, n, reps);
+    return SUPIR_LAUNCH_STATUS();
+}
+
+int supir_dpmpp2m_post_tiles_launch(const float* net_out, const float* x, const float* old, const float* eps, float c_out, float c_skip,
+                                    float cfg, float m1, float m2, float m3, float m4, float noise_mul, float s_noise, float* x_next,
+                                    float* den_out, const SupirTileList& tl, int b, int C, int Hc, int Wc, int T, int reps, hipStream_t st) {
+    if (tl.n <= 0 || tl.n > SUPIR_MAX_TILES || b <= 0 || C <= 0 || T <= 0 || reps < 1 || reps > 2) return SUPIR_ERR_ARG;
+    for (int j = 0; j < tl.n; ++j)
+        if (tl.hi[j] < 0 || tl.wi[j] < 0 || tl.hi[j] + T > Hc || tl.wi[j] + T > Wc) return SUPIR_ERR_SHAPE;
+    if ((long)b * C > 65535) return SUPIR_ERR_SHAPE;
+    SUPIR_LAUNCH(dpmpp_post_tiles_kernel, dim3((unsigned)((T * T + 255) / 256), (unsigned)(b * C), (unsigned)tl.n), dim3(256), 0, st, net_out,
+                 x, old, eps, c_out, c_skip, cfg, m1, m2, m3, m4, noise_mul, s_noise, x_next, den_out, tl, b, C, Hc, Wc, T, reps);
     return SUPIR_LAUNCH_STATUS();
 }

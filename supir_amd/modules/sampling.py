@@ -16,8 +16,9 @@ import torch.nn as nn
 from .brownian import BrownianTreeNoiseSampler
 
 SIGMA_MAX = 14.6146
-# RestoreEDMSampler: run the elementwise halves of a step as two fused kernels (csrc/sampler.hip) with host-side scalars when the
-# caller exposes its denoiser / network (SUPIRModel.batchify_sample does); off -> the generic torch-op path for every caller
+# the switch for BOTH fused sampler steps -- RestoreEDMSampler and RestoreDPMPP2MSampler (+ their tiled forms): run the elementwise
+# halves of a step as fused kernels (csrc/sampler.hip) with host-side scalars when the caller exposes its denoiser / network
+# (SUPIRModel.batchify_sample does); off -> the generic torch-op path for every caller
 FUSED_EDM_STEP = os.environ.get("SUPIR_FUSED_EDM_STEP", "1") == "1"
 # with the fused step: the network prepares the time / label embeddings of ALL steps of an image before the loop
 # (ControlWrapper.prepare_schedule) instead of recomputing them at the head of every step
@@ -196,6 +197,30 @@ class IdentityGuider:
 
 
 # ----------------------------------------------------------------------------------------------- samplers
+def _fused_ctx(guider, denoiser, x):
+    """(denoiser module, network) when a sampler call can take its fused step: fp32 CUDA latents, a caller that exposes what its
+    denoiser closure wraps (`denoiser.fused = (DiscreteDenoiserWithControl, network)`), the guiders SUPIR ships."""
+    f = getattr(denoiser, "fused", None)
+    if not FUSED_EDM_STEP or f is None or not x.is_cuda or x.dtype != torch.float32:
+        return None
+    if not isinstance(guider, (LinearCFG, IdentityGuider)):
+        return None
+    if isinstance(guider, LinearCFG) and not isinstance(guider.dyn_thresh, NoDynamicThresholding):
+        return None
+    den, net = f
+    if not isinstance(den, DiscreteDenoiserWithControl) or den.host_scalars(np.float32(1.0)) is None:
+        return None
+    return den, net
+
+
+def _host_cfg(guider, sigma32):
+    """LinearCFG.scale_schedule(sigma) in fp32 on the host (the torch expression's operation order); 0.0 without a guider."""
+    if isinstance(guider, IdentityGuider):
+        return 0.0
+    f32 = np.float32
+    return float(f32(guider.scale - guider.scale_min) * sigma32 / f32(SIGMA_MAX) + f32(guider.scale_min))
+
+
 class BaseDiffusionSampler:
     def __init__(self, discretization_config=None, num_steps=None, guider_config=None, verbose=False, device="cuda"):
         self.num_steps = num_steps
@@ -254,19 +279,7 @@ class RestoreEDMSampler(BaseDiffusionSampler):
 
     # ------------------------------------------------------------------ fused step (two elementwise kernels + the network call)
     def _fused_ctx(self, denoiser, x):
-        """(denoiser module, network) when this call can take the fused step: fp32 CUDA latents, a caller that exposes what its
-        denoiser closure wraps (`denoiser.fused = (DiscreteDenoiserWithControl, network)`), the guiders SUPIR ships."""
-        f = getattr(denoiser, "fused", None)
-        if not FUSED_EDM_STEP or f is None or not x.is_cuda or x.dtype != torch.float32:
-            return None
-        if not isinstance(self.guider, (LinearCFG, IdentityGuider)):
-            return None
-        if isinstance(self.guider, LinearCFG) and not isinstance(self.guider.dyn_thresh, NoDynamicThresholding):
-            return None
-        den, net = f
-        if not isinstance(den, DiscreteDenoiserWithControl) or den.host_scalars(np.float32(1.0)) is None:
-            return None
-        return den, net
+        return _fused_ctx(self.guider, denoiser, x)
 
     def _fused_step(self, ctx, sigma_f, next_sigma_f, x, gamma, x_center, eps_noise, control_scale, use_linear_control_scale,
                     control_scale_start, cond_cat, sched_row=None, tiles=None):
@@ -298,10 +311,7 @@ class RestoreEDMSampler(BaseDiffusionSampler):
         if sched_row is not None:
             net.select_step(sched_row, idx)     # this call's timestep embeddings come out of the per-image table (ControlWrapper.prepare_schedule)
         out = net(net_in, den.idx_tensor(idx, net_in.shape[0], x.device), cond_cat, control_scale)
-        cfg = 0.0
-        if twice:
-            g = self.guider
-            cfg = float(f32(g.scale - g.scale_min) * sigma_hat / f32(SIGMA_MAX) + f32(g.scale_min))
+        cfg = _host_cfg(self.guider, sigma_hat)
         center, restore_mul = None, 0.0
         if (next_sigma_f > self.restore_cfg_s_tmin) and (self.restore_cfg > 0):
             center = x_center
@@ -363,24 +373,100 @@ def _sliding_windows(h, w, tile_size, tile_stride):
     return [(hi, hi + tile_size, wi, wi + tile_size) for hi in hi_list for wi in wi_list]
 
 
-class TiledRestoreEDMSampler(RestoreEDMSampler):
+def _stack(t, grp):
+    """torch.cat of the tile windows `grp` = [(hi, he, wi, we)] of t along dim 0 (tile j, sample i at row j*b + i)."""
+    return torch.cat([t[:, :, a:b_, c:d] for (a, b_, c, d) in grp], 0)
+
+
+class _TileGroups:
+    """What the two tiled samplers share around their per-tile step: tile batching (`tile_batch`), tile-parallel ranks
+    (`tile_parallel`, `process_group`), the normalising count canvas and the repeated conditioning of a group of stacked tiles."""
+
+    def _init_tiling(self, tile_size, tile_stride, tile_batch, tile_parallel, process_group):
+        self.tile_size, self.tile_stride = tile_size, tile_stride
+        # SURVEY 8(f).1: with `tile_parallel` and an initialised torch.distributed group, the tile groups of a step are dealt
+        # round-robin to the ranks (one process per GPU); every rank blends its own tiles into a zero canvas and ONE all-reduce
+        # (sum, RCCL) of that canvas per step assembles x_next -- the only exchange the algorithm needs (the normalising
+        # `count` canvas is tile-geometry only, computed locally).  Rank 0's start latent and per-step noise are broadcast
+        # so the ranks cannot drift apart even if their RNG streams differ.
+        self.tile_parallel = bool(tile_parallel)
+        self.process_group = process_group
+        # tiles of one step are independent given x and the step's noise (sampling.py:629-657, 705-726): `tile_batch` > 1 stacks
+        # that many tiles along the batch axis of ONE denoiser call (M of every GEMM grows k-fold, 49 -> ceil(49/k) launches of
+        # the network per step); per-tile arithmetic is unchanged, so the result is identical.
+        self.tile_batch = max(1, int(tile_batch))
+
+    def _tile_ranks(self, x):
+        """(x, shared, world, rank, src): with tile-parallel ranks, x becomes rank src's start latent (broadcast in place)."""
+        import torch.distributed as dist
+        from ..parallel import collectives_active
+        world, rank, src = 1, 0, 0
+        shared = self.tile_parallel and collectives_active(self.process_group)   # > 1 rank (or a forced 1-rank group: RCCL test)
+        if shared:
+            world, rank = dist.get_world_size(self.process_group), dist.get_rank(self.process_group)
+            src = dist.get_global_rank(self.process_group, 0) if self.process_group is not None else 0
+            x = x.contiguous()
+            dist.broadcast(x, src=src, group=self.process_group)
+        return x, shared, world, rank, src
+
+    @staticmethod
+    def _tile_groups(tiles, kb, world, rank):
+        """The groups of kb consecutive tiles one network call stacks, and the indices of the groups this rank runs (round robin)."""
+        groups = [tiles[j0:j0 + kb] for j0 in range(0, len(tiles), kb)]
+        return groups, [gi for gi in range(len(groups)) if world == 1 or gi % world == rank]
+
+    @staticmethod
+    def _count_canvas(x, tiles, tile_weights):
+        """sum of the tile weights over every tile of the canvas, in tile order (what the reference accumulates every step)."""
+        count = torch.zeros_like(x)
+        for (hi, he, wi, we) in tiles:
+            count[:, :, hi:he, wi:we] += tile_weights
+        return count
+
+    def _group_cat(self, static, lq, grp):
+        """The conditioning of one network call on the stacked tiles grp: repeated text / vector halves + the stacked LQ windows."""
+        k = len(grp)
+        ctl = _stack(lq, grp)
+        cat = self._static_rep(static, k) if k > 1 else dict(static)
+        cat["control"] = torch.cat((ctl, ctl), 0) if not isinstance(self.guider, IdentityGuider) else ctl
+        return cat
+
+    @staticmethod
+    def _group_schedules(net, t_all, groups, mine, cats):
+        """One per-image embedding table per group size (all tiles share the timestep; the LQ windows differ per group: no cached
+        hint).  True when prepared."""
+        seen = set()
+        for gi in mine:
+            k = len(groups[gi])
+            if k not in seen:
+                seen.add(k)
+                net.prepare_schedule(t_all, cats[gi]["vector"])
+        return True
+
+    def _static_rep(self, cat, k):
+        """[uncond; cond] text / vector conditioning repeated for k stacked tiles: [uc]*k ; [c]*k (cached per k, so the
+        network's per-context caches and its hipGraph see the same tensors every step)."""
+        cache = self.__dict__.setdefault("_rep_cache", {})
+        key = (id(cat), k)
+        if key not in cache:
+            rep = {}
+            for name, v in cat.items():
+                if name == "control" or not torch.is_tensor(v):
+                    continue
+                u, c = v.chunk(2, 0) if not isinstance(self.guider, IdentityGuider) else (v, None)
+                rep[name] = torch.cat([u.repeat(k, *([1] * (v.dim() - 1))), c.repeat(k, *([1] * (v.dim() - 1)))], 0).contiguous() \
+                    if c is not None else u.repeat(k, *([1] * (v.dim() - 1))).contiguous()
+            cache[key] = (cat, rep)   # keep `cat` alive: the key uses its id
+        return dict(cache[key][1])
+
+
+class TiledRestoreEDMSampler(_TileGroups, RestoreEDMSampler):
     """sampling.py:600-660: per step, every 128x128 latent tile takes a full sampler step; Gaussian-weighted blend."""
 
     def __init__(self, tile_size=128, tile_stride=64, *args, tile_batch=1, tile_parallel=False, process_group=None, **kwargs):
         super().__init__(*args, **kwargs)
-        self.tile_size, self.tile_stride = tile_size, tile_stride
+        self._init_tiling(tile_size, tile_stride, tile_batch, tile_parallel, process_group)
         self.tile_weights = None
-        # SURVEY 8(f).1: with `tile_parallel` and an initialised torch.distributed group, the tile groups of a step are dealt
-        # round-robin to the ranks (one process per GPU); every rank blends its own tiles into a zero canvas and ONE all-reduce
-        # (sum, RCCL) of that canvas per step assembles x_next -- the only exchange the algorithm needs (the normalising
-        # `count` canvas is tile-geometry only, computed locally).  Rank 0's start latent and per-step churn noise are broadcast
-        # so the ranks cannot drift apart even if their RNG streams differ.
-        self.tile_parallel = bool(tile_parallel)
-        self.process_group = process_group
-        # tiles of one step are independent given x and eps_noise (sampling.py:629-657): `tile_batch` > 1 stacks that many
-        # tiles along the batch axis of ONE denoiser call (M of every GEMM grows k-fold, 49 -> ceil(49/k) launches of the
-        # network per step); per-tile arithmetic is unchanged, so the result is identical.
-        self.tile_batch = max(1, int(tile_batch))
 
     def __call__(self, denoiser, x, cond, uc=None, num_steps=None, x_center=None, control_scale=1.0,
                  use_linear_control_scale=False, control_scale_start=0.0):
@@ -406,17 +492,8 @@ class TiledRestoreEDMSampler(RestoreEDMSampler):
                                            {k: v for k, v in uc.items() if k != "control"})
             static.append(cat)
         import torch.distributed as dist
-        from ..parallel import collectives_active
-        world, rank = 1, 0
-        shared = self.tile_parallel and collectives_active(self.process_group)   # > 1 rank (or a forced 1-rank group: RCCL test)
-        if shared:
-            world, rank = dist.get_world_size(self.process_group), dist.get_rank(self.process_group)
+        x, shared, world, rank, src = self._tile_ranks(x)
         kb = 1 if use_local_prompt else self.tile_batch
-        src = 0
-        if shared:
-            src = dist.get_global_rank(self.process_group, 0) if self.process_group is not None else 0
-            x = x.contiguous()
-            dist.broadcast(x, src=src, group=self.process_group)
         ctx = None
         # the fused step's two tile kernels stack at most 64 tiles per group (SUPIR_MAX_TILES, csrc/kernels.h) and take exact T x T windows
         # inside the canvas; anything else (tile_batch > 64, a canvas smaller than a tile) runs the generic loop below
@@ -427,9 +504,8 @@ class TiledRestoreEDMSampler(RestoreEDMSampler):
             return self._call_fused(ctx, x, tiles, tile_weights, lq, static[0], sf, num_sigmas, x_center, control_scale,
                                     use_linear_control_scale, control_scale_start, kb, shared, world, rank, src)
         if shared:
-            count_all = torch.zeros_like(x)
-            for (hi, he, wi, we) in tiles:
-                count_all[:, :, hi:he, wi:we] += tile_weights
+            count_all = self._count_canvas(x, tiles, tile_weights)
+        groups, mine = self._tile_groups(tiles, kb, world, rank)
         for i in range(num_sigmas - 1):
             gamma = self._gamma(sf[i], num_sigmas)
             x_next = torch.zeros_like(x)
@@ -437,11 +513,9 @@ class TiledRestoreEDMSampler(RestoreEDMSampler):
             eps_noise = torch.randn_like(x)
             if shared:
                 dist.broadcast(eps_noise, src=src, group=self.process_group)
-            for gi, j0 in enumerate(range(0, len(tiles), kb)):
-                if world > 1 and gi % world != rank:
-                    continue
-                grp = tiles[j0:j0 + kb]
-                k = len(grp)
+            for gi in mine:
+                grp = groups[gi]
+                j0, k = gi * kb, len(grp)
                 if k == 1:
                     hi, he, wi, we = grp[0]
                     cj = conds[j0] if use_local_prompt else conds[0]
@@ -457,14 +531,10 @@ class TiledRestoreEDMSampler(RestoreEDMSampler):
                                            next_sigma_f=sf[i + 1])
                     outs = [_x]
                 else:
-                    def stack(t):
-                        return torch.cat([t[:, :, a:b_, c:d] for (a, b_, c, d) in grp], 0)
-                    ctl = stack(lq)
-                    cat = self._static_rep(static[0], k)
-                    cat["control"] = torch.cat((ctl, ctl), 0) if not isinstance(self.guider, IdentityGuider) else ctl
+                    cat = self._group_cat(static[0], lq, grp)
                     s_k = s_in.repeat(k)
-                    _x = self.sampler_step(s_k * sigmas[i], s_k * sigmas[i + 1], denoiser, stack(x), conds[0], uc, gamma,
-                                           stack(x_center), eps_noise=stack(eps_noise), control_scale=control_scale,
+                    _x = self.sampler_step(s_k * sigmas[i], s_k * sigmas[i + 1], denoiser, _stack(x, grp), conds[0], uc, gamma,
+                                           _stack(x_center, grp), eps_noise=_stack(eps_noise, grp), control_scale=control_scale,
                                            use_linear_control_scale=use_linear_control_scale,
                                            control_scale_start=control_scale_start, cond_cat=cat, sigma_f=sf[i],
                                            next_sigma_f=sf[i + 1])
@@ -491,36 +561,15 @@ class TiledRestoreEDMSampler(RestoreEDMSampler):
         import torch.distributed as dist
         from .. import ops
         T = self.tile_size
-        twice = not isinstance(self.guider, IdentityGuider)
-        groups = [tiles[j0:j0 + kb] for j0 in range(0, len(tiles), kb)]
-        mine = [gi for gi in range(len(groups)) if world == 1 or gi % world == rank]
+        groups, mine = self._tile_groups(tiles, kb, world, rank)
         w64 = tile_weights[0, 0].contiguous()
-        count = torch.zeros_like(x)
-        for (hi, he, wi, we) in tiles:
-            count[:, :, hi:he, wi:we] += tile_weights
-
-        def stack(t, grp):
-            return torch.cat([t[:, :, a:b_, c:d] for (a, b_, c, d) in grp], 0)
-
-        gstat = {}
-        for gi in mine:
-            grp = groups[gi]
-            k = len(grp)
-            ctl = stack(lq, grp)
-            cat = self._static_rep(static, k) if k > 1 else dict(static)
-            cat["control"] = torch.cat((ctl, ctl), 0) if twice else ctl
-            gstat[gi] = (cat, stack(x_center, grp).float().contiguous())
+        count = self._count_canvas(x, tiles, tile_weights)
+        gstat = {gi: (self._group_cat(static, lq, groups[gi]), _stack(x_center, groups[gi]).float().contiguous()) for gi in mine}
         sched = False
         if mine and EMB_SCHEDULE and hasattr(ctx[1], "prepare_schedule") and "vector" in static:
             f32 = np.float32
             t_all = [ctx[0].host_scalars(f32(sf[i]) * f32(self._gamma(sf[i], num_sigmas) + 1.0))[0] for i in range(num_sigmas - 1)]
-            seen = set()
-            for gi in mine:      # one table per group size (all tiles share the timestep); the LQ windows differ per group: no cached hint
-                k = len(groups[gi])
-                if k not in seen:
-                    seen.add(k)
-                    ctx[1].prepare_schedule(t_all, gstat[gi][0]["vector"])
-            sched = True
+            sched = self._group_schedules(ctx[1], t_all, groups, mine, {gi: gstat[gi][0] for gi in mine})
         try:
             for i in range(num_sigmas - 1):
                 gamma = self._gamma(sf[i], num_sigmas)
@@ -541,22 +590,6 @@ class TiledRestoreEDMSampler(RestoreEDMSampler):
             if sched:
                 ctx[1].end_schedule()
         return x
-
-    def _static_rep(self, cat, k):
-        """[uncond; cond] text / vector conditioning repeated for k stacked tiles: [uc]*k ; [c]*k (cached per k, so the
-        network's per-context caches and its hipGraph see the same tensors every step)."""
-        cache = self.__dict__.setdefault("_rep_cache", {})
-        key = (id(cat), k)
-        if key not in cache:
-            rep = {}
-            for name, v in cat.items():
-                if name == "control" or not torch.is_tensor(v):
-                    continue
-                u, c = v.chunk(2, 0) if not isinstance(self.guider, IdentityGuider) else (v, None)
-                rep[name] = torch.cat([u.repeat(k, *([1] * (v.dim() - 1))), c.repeat(k, *([1] * (v.dim() - 1)))], 0).contiguous() \
-                    if c is not None else u.repeat(k, *([1] * (v.dim() - 1))).contiguous()
-            cache[key] = (cat, rep)   # keep `cat` alive: the key uses its id
-        return dict(cache[key][1])
 
 
 # ----------------------------------------------------------------------------------------------- DPM++ 2M restore sampler
@@ -674,10 +707,75 @@ class RestoreDPMPP2MSampler(BaseDiffusionSampler):
         sig_host = get_sigmas_karras(n, smin, smax, device="cpu")
         return x, s_in, sig_host.to(x.device), num_sigmas, cond, uc, [float(v) for v in sig_host], smin, smax
 
+    # ------------------------------------------------------------------ fused step (edm_step_pre + the network call + one post kernel)
+    def _fused_ctx(self, denoiser, x):
+        if type(self).sampler_step is not RestoreDPMPP2MSampler.sampler_step:
+            return None
+        return _fused_ctx(self.guider, denoiser, x)
+
+    def _host_step(self, den, sf, i):
+        """Every scalar of step i, on the host: (table index, c_skip, c_out, c_in) of the snapped sigma, the CFG scale of the Karras
+        sigma, [m1, m2, m3, m4] and noise_mul.  The solver factors come from get_variables / get_mult themselves, fed fp32 0-dim
+        host tensors: sampler_step's expressions in its operation order, without a device round trip."""
+        f32 = np.float32
+        idx, c_skip, c_out, c_in = den.host_scalars(f32(sf[i]))
+        sigma, nxt = torch.tensor(sf[i], dtype=torch.float32), torch.tensor(sf[i + 1], dtype=torch.float32)
+        prev = None if i == 0 else torch.tensor(sf[i - 1], dtype=torch.float32)
+        h, r, t, t_next = self.get_variables(sigma, nxt, prev)
+        m = [float(v) for v in self.get_mult(h, r, t, t_next, prev)]
+        noise_mul = float(nxt * (-2 * (self.eta * h)).expm1().neg().sqrt())
+        return idx, c_skip, c_out, c_in, _host_cfg(self.guider, f32(sf[i])), m + [0.0] * (4 - len(m)), noise_mul
+
+    def _fused_step(self, ctx, st, x, old, eps, cond_cat, control_scale, sched_row=None, tiles=None):
+        """sampler_step (sampling.py:429-483) as supir_edm_step_pre (no churn: x * c_in for every CFG copy), the network call and
+        supir_dpmpp2m_step_post; st = _host_step(...).  old None: the first / last step's x_standard; eps None: no noise term.
+        tiles = (windows, T): x / old / eps are canvases and the step runs on the k stacked windows (the _tiles kernels crop).
+        Returns (x_next, denoised) -- stacked tiles with `tiles`."""
+        from .. import ops
+        den, net = ctx
+        idx, c_skip, c_out, c_in, cfg, m, noise_mul = st
+        reps = 1 if isinstance(self.guider, IdentityGuider) else 2
+        if tiles is not None:
+            x_in, net_in = ops.edm_step_pre_tiles(x, None, tiles[0], tiles[1], self.s_noise, 0.0, c_in, reps)
+        else:
+            x_in, net_in = ops.edm_step_pre(x, None, self.s_noise, 0.0, c_in, reps)
+        if sched_row is not None:
+            net.select_step(sched_row, idx)
+        out = net(net_in, den.idx_tensor(idx, net_in.shape[0], x.device), cond_cat, control_scale).float().contiguous()
+        if old is None or not self.eta:
+            eps = None
+        if tiles is not None:
+            return ops.dpmpp2m_step_post_tiles(out, x_in, old, eps, tiles[0], c_out, c_skip, cfg, *m, noise_mul, self.s_noise, reps)
+        return ops.dpmpp2m_step_post(out, x_in, old, eps, c_out, c_skip, cfg, *m, noise_mul, self.s_noise, reps)
+
+    def _call_fused(self, ctx, x, s_in, sigmas, num_sigmas, sf, cond_cat, noise_sampler, control_scale):
+        """__call__'s loop on the fused step, with the per-image embedding schedule (ControlWrapper.prepare_schedule) prepared from the
+        table index of every Karras sigma.  Noise-sampler queries (arguments, order, conditions) are the generic loop's."""
+        den, net = ctx
+        steps = [self._host_step(den, sf, i) for i in range(num_sigmas - 1)]
+        sched = False
+        if EMB_SCHEDULE and hasattr(net, "prepare_schedule") and "vector" in cond_cat:
+            net.prepare_schedule([s[0] for s in steps], cond_cat["vector"], control=cond_cat.get("control"))
+            sched = True
+        x = x.contiguous()
+        old = None
+        try:
+            for i in range(num_sigmas - 1):
+                eps = noise_sampler(s_in * sigmas[i], s_in * sigmas[i + 1]) if (i > 0 and sf[i + 1] > 1e-14) else None
+                x, old = self._fused_step(ctx, steps[i], x, None if sf[i + 1] < 1e-14 else old, eps, cond_cat, control_scale,
+                                          sched_row=i if sched else None)
+        finally:
+            if sched:
+                net.end_schedule()
+        return x
+
     def __call__(self, denoiser, x, cond, uc=None, num_steps=None, control_scale=1.0, **kwargs):
         x, s_in, sigmas, num_sigmas, cond, uc, sf, smin, smax = self._karras(x, cond, uc, num_steps)
         cond_cat = self.guider.prepare_cond(cond, uc)
         noise_sampler = self.noise_sampler_cls(x, smin, smax)
+        ctx = self._fused_ctx(denoiser, x)
+        if ctx is not None:
+            return self._call_fused(ctx, x, s_in, sigmas, num_sigmas, sf, cond_cat, noise_sampler, control_scale)
         old = None
         for i in range(num_sigmas - 1):
             eps = noise_sampler(s_in * sigmas[i], s_in * sigmas[i + 1]) if (i > 0 and sf[i + 1] > 1e-14) else None
@@ -687,15 +785,19 @@ class RestoreDPMPP2MSampler(BaseDiffusionSampler):
         return x
 
 
-class TiledRestoreDPMPP2MSampler(RestoreDPMPP2MSampler):
-    """sampling.py:663-730: tile loop + Gaussian blend around the DPM++ step (x and old_denoised are both blended)."""
+class TiledRestoreDPMPP2MSampler(_TileGroups, RestoreDPMPP2MSampler):
+    """sampling.py:663-730: tile loop + Gaussian blend around the DPM++ step (x and old_denoised are both blended).  tile_batch /
+    tile_parallel / process_group as on TiledRestoreEDMSampler: k tiles per network call, tile groups dealt round robin to the ranks
+    with ONE all-reduce per step (x_next and old_next stacked in one buffer); rank 0's start latent and per-step noise are broadcast."""
 
-    def __init__(self, tile_size=128, tile_stride=64, *args, **kwargs):
+    def __init__(self, tile_size=128, tile_stride=64, *args, tile_batch=1, tile_parallel=False, process_group=None, **kwargs):
         super().__init__(*args, **kwargs)
-        self.tile_size, self.tile_stride = tile_size, tile_stride
+        self._init_tiling(tile_size, tile_stride, tile_batch, tile_parallel, process_group)
 
     def __call__(self, denoiser, x, cond, uc=None, num_steps=None, control_scale=1.0, **kwargs):
+        import torch.distributed as dist
         use_local_prompt = isinstance(cond, list)
+        self.__dict__["_rep_cache"] = {}   # per call, like TiledRestoreEDMSampler's
         b, _, h, w = x.shape
         tiles = _sliding_windows(h, w, self.tile_size, self.tile_stride)
         tile_weights = gaussian_weights(self.tile_size, self.tile_size, 1, device=x.device).repeat(b, 1, 1, 1)
@@ -705,25 +807,97 @@ class TiledRestoreDPMPP2MSampler(RestoreDPMPP2MSampler):
         conds = [dict(cj) for cj in cond] if use_local_prompt else [dict(cond)]
         static = [self.guider.prepare_cond({k: v for k, v in cj.items() if k != "control"},
                                            {k: v for k, v in uc.items() if k != "control"}) for cj in conds]
+        x, shared, world, rank, src = self._tile_ranks(x)
+        kb = 1 if use_local_prompt else self.tile_batch
+        groups, mine = self._tile_groups(tiles, kb, world, rank)
+        count = self._count_canvas(x, tiles, tile_weights)
         noise_sampler = self.noise_sampler_cls(x, smin, smax)
+        ctx = None
+        # the tile kernels stack at most 64 tiles per group and take exact T x T windows inside the canvas (as for EDM)
+        if kb <= 64 and h >= self.tile_size and w >= self.tile_size and not use_local_prompt:
+            ctx = self._fused_ctx(denoiser, x)
+        if ctx is not None:
+            return self._call_fused_tiles(ctx, x, s_in, sigmas, num_sigmas, sf, tile_weights, count, lq, static[0], groups, mine,
+                                          noise_sampler, control_scale, shared, src)
         old = None
         for i in range(num_sigmas - 1):
-            eps = noise_sampler(s_in * sigmas[i], s_in * sigmas[i + 1]) if (i > 0 and sf[i + 1] > 1e-14) else torch.zeros_like(x)
-            x_next, old_next, count = torch.zeros_like(x), torch.zeros_like(x), torch.zeros_like(x)
-            for j, (hi, he, wi, we) in enumerate(tiles):
-                cj = conds[j] if use_local_prompt else conds[0]
-                ctl = lq[:, :, hi:he, wi:we]
-                cj["control"] = ctl
-                uc["control"] = ctl
-                cat = dict(static[j if use_local_prompt else 0])
-                cat["control"] = torch.cat((ctl, ctl), 0) if not isinstance(self.guider, IdentityGuider) else ctl
-                _x, _old = self.sampler_step(None if old is None else old[:, :, hi:he, wi:we],
-                                             None if i == 0 else s_in * sigmas[i - 1], s_in * sigmas[i], s_in * sigmas[i + 1],
-                                             denoiser, x[:, :, hi:he, wi:we], cj, uc=uc, eps_noise=eps[:, :, hi:he, wi:we],
-                                             control_scale=control_scale, cond_cat=cat, last=sf[i + 1] < 1e-14)
-                x_next[:, :, hi:he, wi:we] += _x * tile_weights
-                old_next[:, :, hi:he, wi:we] += _old * tile_weights
-                count[:, :, hi:he, wi:we] += tile_weights
+            noisy = i > 0 and sf[i + 1] > 1e-14
+            eps = noise_sampler(s_in * sigmas[i], s_in * sigmas[i + 1]) if noisy else torch.zeros_like(x)
+            if shared and noisy:
+                eps = eps.contiguous()
+                dist.broadcast(eps, src=src, group=self.process_group)
+            buf = x.new_zeros((2,) + tuple(x.shape))      # x_next ; old_next: one all-reduce for both
+            x_next, old_next = buf[0], buf[1]
+            last = sf[i + 1] < 1e-14
+            for gi in mine:
+                grp = groups[gi]
+                j0, k = gi * kb, len(grp)
+                if k == 1:
+                    hi, he, wi, we = grp[0]
+                    cj = conds[j0] if use_local_prompt else conds[0]
+                    ctl = lq[:, :, hi:he, wi:we]
+                    cj["control"] = ctl
+                    uc["control"] = ctl
+                    cat = dict(static[j0 if use_local_prompt else 0])
+                    cat["control"] = torch.cat((ctl, ctl), 0) if not isinstance(self.guider, IdentityGuider) else ctl
+                    _x, _old = self.sampler_step(None if old is None else old[:, :, hi:he, wi:we],
+                                                 None if i == 0 else s_in * sigmas[i - 1], s_in * sigmas[i], s_in * sigmas[i + 1],
+                                                 denoiser, x[:, :, hi:he, wi:we], cj, uc=uc, eps_noise=eps[:, :, hi:he, wi:we],
+                                                 control_scale=control_scale, cond_cat=cat, last=last)
+                    outs = [(_x, _old)]
+                else:
+                    s_k = s_in.repeat(k)
+                    _x, _old = self.sampler_step(None if old is None else _stack(old, grp),
+                                                 None if i == 0 else s_k * sigmas[i - 1], s_k * sigmas[i], s_k * sigmas[i + 1],
+                                                 denoiser, _stack(x, grp), conds[0], uc=uc, eps_noise=_stack(eps, grp),
+                                                 control_scale=control_scale, cond_cat=self._group_cat(static[0], lq, grp), last=last)
+                    outs = list(zip(_x.chunk(k, 0), _old.chunk(k, 0)))
+                for (hi, he, wi, we), (_xt, _ot) in zip(grp, outs):
+                    x_next[:, :, hi:he, wi:we] += _xt * tile_weights
+                    old_next[:, :, hi:he, wi:we] += _ot * tile_weights
+            if shared:
+                dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.process_group)
             old = old_next / count
             x = x_next / count
+        return x
+
+    def _call_fused_tiles(self, ctx, x, s_in, sigmas, num_sigmas, sf, tile_weights, count, lq, static, groups, mine, noise_sampler,
+                          control_scale, shared, src):
+        """The loop of __call__ on the fused step: per tile group ONE supir_edm_step_pre_tiles (crop of x + c_in), the network call
+        (announced to the per-image embedding schedule prepared once per group size; replayed from one hipGraph per group shape when
+        the network has graphs on), ONE supir_dpmpp2m_step_post_tiles (reads old / eps through the windows) and two supir_tile_blend
+        (x_next, old_next).  Each group's stacked LQ windows and repeated text / vector conditioning are built once per call."""
+        import torch.distributed as dist
+        from .. import ops
+        den, net = ctx
+        T = self.tile_size
+        w64 = tile_weights[0, 0].contiguous()
+        cats = {gi: self._group_cat(static, lq, groups[gi]) for gi in mine}
+        steps = [self._host_step(den, sf, i) for i in range(num_sigmas - 1)]
+        sched = False
+        if mine and EMB_SCHEDULE and hasattr(net, "prepare_schedule") and "vector" in static:
+            sched = self._group_schedules(net, [s[0] for s in steps], groups, mine, cats)
+        x = x.contiguous()
+        old = None
+        try:
+            for i in range(num_sigmas - 1):
+                noisy = i > 0 and sf[i + 1] > 1e-14
+                eps = noise_sampler(s_in * sigmas[i], s_in * sigmas[i + 1]) if noisy else None
+                if noisy:
+                    eps = eps.float().contiguous()
+                    if shared:
+                        dist.broadcast(eps, src=src, group=self.process_group)
+                buf = x.new_zeros((2,) + tuple(x.shape))
+                for gi in mine:
+                    xn, dn = self._fused_step(ctx, steps[i], x, None if sf[i + 1] < 1e-14 else old, eps, cats[gi], control_scale,
+                                              sched_row=i if sched else None, tiles=(groups[gi], T))
+                    ops.tile_blend(xn, w64, buf[0], groups[gi], T)
+                    ops.tile_blend(dn, w64, buf[1], groups[gi], T)
+                if shared:
+                    dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.process_group)
+                buf /= count
+                x, old = buf[0], buf[1]
+        finally:
+            if sched:
+                net.end_schedule()
         return x

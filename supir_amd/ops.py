@@ -1564,6 +1564,56 @@ def tile_blend(out_tiles, weights, canvas, tiles, T):
     return canvas
 
 
+def _f32c(t):
+    return t if t is None or (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+
+
+def dpmpp2m_step_post(net_out, x, old, eps, c_out, c_skip, cfg_scale, m1, m2, m3, m4, noise_mul, s_noise, reps):
+    """The post half of one DPM++(2M) step on fp32 latents: den = CFG(net_out * c_out + x * c_skip); old None: x_next = m1 * x - m2 *
+    den, else x_next = m1 * x - m2 * (m3 * den - m4 * old) (+ (eps * noise_mul) * s_noise when eps is given).  Returns (x_next, den)
+    as new tensors.  See supir_dpmpp2m_step_post."""
+    lib = _lib.load()
+    old, eps = _f32c(old), _f32c(eps)
+    _check_dev(net_out, x, old, eps)
+    n = x.numel()
+    assert net_out.dtype == torch.float32 and net_out.is_contiguous() and net_out.numel() == reps * n
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    assert old is None or old.shape == x.shape
+    assert eps is None or eps.shape == x.shape
+    x_next, den = torch.empty_like(x), torch.empty_like(x)
+    _no_defer("dpmpp2m_step_post")
+    rc = lib.supir_dpmpp2m_step_post(net_out.data_ptr(), x.data_ptr(), _p(old), _p(eps), float(c_out), float(c_skip), float(cfg_scale),
+                                     float(m1), float(m2), float(m3), float(m4), float(noise_mul), float(s_noise), x_next.data_ptr(),
+                                     den.data_ptr(), n, reps, _stream())
+    _lib.check(rc, "supir_dpmpp2m_step_post", lib)
+    return x_next, den
+
+
+def dpmpp2m_step_post_tiles(net_out, x, old, eps, tiles, c_out, c_skip, cfg_scale, m1, m2, m3, m4, noise_mul, s_noise, reps):
+    """dpmpp2m_step_post on k stacked tiles: net_out [reps*k*b, C, T, T] and x [k*b, C, T, T] as edm_step_pre_tiles made them; old / eps
+    (None, or fp32 canvases [b, C, Hc, Wc]) are read through the windows `tiles` = [(hi, he, wi, we)].  Returns the stacked (x_next,
+    den).  See supir_dpmpp2m_step_post_tiles."""
+    lib = _lib.load()
+    old, eps = _f32c(old), _f32c(eps)
+    _check_dev(net_out, x, old, eps)
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4
+    k, (kb, C, T, _) = len(tiles), x.shape
+    assert kb % k == 0 and x.shape[3] == T
+    b = kb // k
+    assert net_out.dtype == torch.float32 and net_out.is_contiguous() and tuple(net_out.shape) == (reps * kb, C, T, T)
+    canvas = old if old is not None else eps
+    Hc, Wc = (canvas.shape[2], canvas.shape[3]) if canvas is not None else (max(t[1] for t in tiles), max(t[3] for t in tiles))
+    for t in (old, eps):
+        assert t is None or tuple(t.shape) == (b, C, Hc, Wc)
+    x_next, den = torch.empty_like(x), torch.empty_like(x)
+    _no_defer("dpmpp2m_step_post_tiles")
+    rc = lib.supir_dpmpp2m_step_post_tiles(net_out.data_ptr(), x.data_ptr(), _p(old), _p(eps), float(c_out), float(c_skip), float(cfg_scale),
+                                           float(m1), float(m2), float(m3), float(m4), float(noise_mul), float(s_noise), x_next.data_ptr(),
+                                           den.data_ptr(), _tile_hw(tiles), k, b, C, Hc, Wc, T, reps, _stream())
+    _lib.check(rc, "supir_dpmpp2m_step_post_tiles", lib)
+    return x_next, den
+
+
 def wavelet_decomposition(img, levels=5, want_high=True):
     """(high, low) of SUPIR/utils/colorfix.py:96-107 on fp32 [N,3,H,W]: `levels` launches of supir_wavelet_level (radius 2^i),
     ping-ponging two low-pass buffers; `high` accumulates img_i - low_i in place.  want_high=False skips the high band (the style

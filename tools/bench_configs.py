@@ -4,13 +4,18 @@ the matrix peak (algorithmic TFLOP of BASELINE.md section 2 / seconds / peak).  
   config 1   512 x 512, 2 EDM steps: the ONE config BASELINE quotes in fp32 -> the fp32 service (libsupir_hip_f32.so, `--diff_dtype fp32
              --ae_dtype fp32`, peak = the 157 TFLOP/s of v_mfma_f32_16x16x4_f32) with the bf16 time beside it
   config 5   1024 x 1024, DPM++ 2M restore sampler, 8 and 4 steps, diff_dtype fp16 (options/SUPIR_v0_Juggernautv9_lightning.yaml:5) with bf16 beside
+             + the fused DPM++ step on / off (fp16, alternating in one process)
   config 3   4096 x 4096, TiledRestoreEDMSampler 128 / 64 (49 tiles) + tiled VAE (512 / 64), 50 steps, bf16
+  config 6   4096 x 4096, TiledRestoreDPMPP2MSampler (the Lightning sampler) 128 / 64 (49 tiles) + tiled VAE, 8 steps, fp16 network;
+             tile_batch 1 and 4, the fused step on / off alternating (not a BASELINE.json entry: config 5's sampler at config 3's size)
 
-Usage: python tools/bench_configs.py [--configs 1,5,3] [--tiled-steps 50] [--tile-batch 4] [--out gpurun_out/other_configs.json]"""
+Usage: python tools/bench_configs.py [--configs 1,5,3,6] [--tiled-steps 50] [--tile-batch 4] [--lightning-steps 8] [--ab-reps 3]
+       [--out FILE.json]"""
 import argparse
 import json
 import math
 import os
+import statistics
 import sys
 import time
 
@@ -26,6 +31,8 @@ ap.add_argument("--configs", default="1,5,3")
 ap.add_argument("--tiled-steps", type=int, default=50)
 ap.add_argument("--tile-batch", type=int, default=4)
 ap.add_argument("--tiled-res", type=int, default=4096)
+ap.add_argument("--lightning-steps", type=int, default=8)     # config 6
+ap.add_argument("--ab-reps", type=int, default=3)             # fused on / off alternations (configs 5 and 6)
 ap.add_argument("--out", default="gpurun_out/other_configs.json")
 args = ap.parse_args()
 want = {int(c) for c in args.configs.split(",")}
@@ -91,6 +98,28 @@ if 1 in want:
     m.model.dtype, m.ae_dtype = torch.bfloat16, torch.bfloat16
     m.model.enable_graph(True)
     print(json.dumps(res), flush=True)
+
+
+def fused_ab(timed, reps):
+    """timed(fused) -> (seconds, output) for the DPM++ sampler with its fused step on / off, alternating on / off `reps` times in this
+    process (same warm state, same seeds): per-mode times, their spread, and the rel-L2 of the last outputs of the two modes."""
+    from supir_amd.modules import sampling
+    times, outs = {True: [], False: []}, {}
+    try:
+        for _ in range(reps):
+            for fused in (True, False):
+                sampling.FUSED_EDM_STEP = fused
+                s, outs[fused] = timed(fused)
+                times[fused].append(round(s, 4))
+    finally:
+        sampling.FUSED_EDM_STEP = True
+    a, b = outs[True].float(), outs[False].float()
+    return dict(s_fused=times[True], s_generic=times[False], median_fused=round(statistics.median(times[True]), 4),
+                median_generic=round(statistics.median(times[False]), 4), spread_fused=round(max(times[True]) - min(times[True]), 4),
+                spread_generic=round(max(times[False]) - min(times[False]), 4),
+                rel_l2_fused_vs_generic=float((a - b).norm() / b.norm()), finite=bool(torch.isfinite(a).all() and torch.isfinite(b).all()))
+
+
 if 5 in want:
     m.sampler_config["target"] = "sgm.modules.diffusionmodules.sampling.RestoreDPMPP2MSampler"
     m.sampler_config["params"]["eta"] = 1.0
@@ -101,6 +130,22 @@ if 5 in want:
             s, ok = run(m, 1024, steps, reps=2, cfg_scale=2.0, cfg_scale_start=2.0)
             res[f"config5_1024px_dpmpp2m_{steps}steps_{name}"] = entry(s, image_tflop(1024, steps), name, finite=ok,
                                                                       noise="brownian.BrownianTreeNoiseSampler (k-diffusion / torchsde absent)")
+        print(json.dumps(res), flush=True)
+    # the fused DPM++ step (csrc/sampler.hip) on / off, fp16 network, same seed
+    m.model.dtype = torch.float16
+    x5 = synth_tensor("img1024", (1, 3, 1024, 1024), scale=0.5).clamp(-1, 1).to(dev)
+    for steps in (8, 4):
+        kw5 = dict(cond=cond(), num_steps=steps, restoration_scale=-1, s_churn=0, s_noise=1.003, cfg_scale=2.0, seed=1234,
+                   color_fix_type="Wavelet", use_linear_CFG=True, cfg_scale_start=2.0)
+
+        def timed5(fused, kw5=kw5):
+            torch.cuda.synchronize()
+            t0 = time.time()
+            out = m.batchify_sample(x5, **kw5)
+            torch.cuda.synchronize()
+            return time.time() - t0, out
+
+        res[f"config5_1024px_dpmpp2m_{steps}steps_fp16_fused_ab"] = fused_ab(timed5, args.ab_reps)
         print(json.dumps(res), flush=True)
     m.model.dtype = torch.bfloat16
     m.sampler_config["params"].pop("eta", None)
@@ -133,5 +178,39 @@ if 3 in want:
                                              vae_tiles_enc_dec=[n_enc, n_dec], s_warmup_call_2_steps=round(t_first, 1),
                                              finite=bool(torch.isfinite(out).all()), peak_mem_GB=round(torch.cuda.max_memory_allocated() / 1e9, 1))
     print(json.dumps(res), flush=True)
+if 6 in want:
+    # the Lightning sampler (options/SUPIR_v0_Juggernautv9_lightning.yaml: DPM++ 2M, s_noise 1.003, LinearCFG 7.5 -> 4.0, fp16 network)
+    # tiled like config 3: 128 / 64 latent tiles + tiled VAE, 8 steps; tile_batch 1 vs 4, fused step on / off alternating
+    m.sampler_config["target"] = "sgm.modules.diffusionmodules.sampling.TiledRestoreDPMPP2MSampler"
+    m.sampler_config["params"].update(tile_size=128, tile_stride=64, eta=1.0)
+    if not hasattr(m.first_stage_model.decoder, "original_forward"):
+        m.init_tile_vae(encoder_tile_size=512, decoder_tile_size=64)
+    m.model.dtype = torch.float16
+    torch.cuda.reset_peak_memory_stats()
+    R = args.tiled_res
+    lat = R // 8
+    n_tiles = (math.ceil((lat - 128) / 64) + 1) ** 2
+    x6 = synth_tensor(f"img{R}", (1, 3, R, R), scale=0.5).clamp(-1, 1).to(dev)
+    kw6 = dict(cond=cond(), restoration_scale=-1, s_churn=0, s_noise=1.003, cfg_scale=4.0, cfg_scale_start=7.5, use_linear_CFG=True,
+               seed=1234, color_fix_type="Wavelet")
+    for tb in (1, 4):
+        m.sampler_config["params"]["tile_batch"] = tb
+        t0 = time.time()
+        m.batchify_sample(x6, num_steps=2, **kw6)                          # warm-up: autotune, graph capture for this group shape
+        torch.cuda.synchronize()
+        t_first = time.time() - t0
+
+        def timed6(fused):
+            torch.cuda.synchronize()
+            t0 = time.time()
+            out = m.batchify_sample(x6, num_steps=args.lightning_steps, **kw6)
+            torch.cuda.synchronize()
+            return time.time() - t0, out
+
+        res[f"config6_{R}px_tiled_dpmpp2m_{args.lightning_steps}steps_fp16_tile_batch{tb}"] = dict(
+            fused_ab(timed6, args.ab_reps), tile_batch=tb, latent_tiles=n_tiles, s_warmup_call_2_steps=round(t_first, 1),
+            peak_mem_GB=round(torch.cuda.max_memory_allocated() / 1e9, 1))
+        print(json.dumps(res), flush=True)
+    m.model.dtype = torch.bfloat16
 os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
 json.dump(res, open(args.out, "w"), indent=1)
