@@ -7,14 +7,17 @@
 // SIMDs share one 128 B/clk LDS, so TM TN / (TM + TN) must exceed 32 before the matrix pipe can be the limit (plus ~30 % for the
 // global->LDS fill, which uses the same port).  Eight waves of 32 x 160 (tile 34) sit at 26.7: 976 LDS cycles per 640 MFMA
 // cycles.  Here: tile 256 x 320 = (2048 / 256) x (10240 / 320) = exactly 256 workgroups, eight waves as 4 (M) x 2 (N), each
-// 64 tokens x 160 channels = 2 x 5 blocks of v_mfma_f32_32x32x16_bf16 (160 accumulator registers, two waves per SIMD):
+// 64 tokens x 160 channels = 4 x 10 blocks of v_mfma_f32_16x16x32_bf16 (160 accumulator registers, two waves per SIMD):
 // intensity 45.7, 592 LDS cycles per 640 MFMA cycles.  Both operands go through a 2-deep global_load_lds ring (72 KB per
-// 64-wide K step), swizzled as in gemm.hip; fragment reads run two MFMA pairs ahead of their use.
+// 64-wide K step), swizzled as in gemm.hip; fragment reads run two MFMA quads ahead of their use.
+// The 16x16x32 form does the 32x32x16 form's work in the same cycles and with the same fragment bytes (14 x 1 KB per wave and
+// 32-wide K slice either way), but draws less power per FLOP: the step is power-limited, so the same cycles run at a higher clock.
 // (Measured and rejected: loading the activation fragments global -> VGPR directly, bypassing LDS.  A fragment wants one token
 // row per lane, so every wave-level load touches 32 cache lines for 32 bytes each and each line is fetched four times per K
 // step: 72.9 us against 57.0 us for tile 34 -- the texture-address path and the L2 saturate long before the matrix pipe.)
-// Epilogue = the GEGLU epilogue of gemm16.hip (LayerNorm fold, bias, value * gelu(gate) with the 16-row value / gate
-// interleave of weights.interleave_geglu(block=16), bf16 rows staged through LDS for 16-byte stores).
+// Epilogue: LayerNorm fold, bias, value * gelu(gate) with the 16-row value / gate interleave of weights.interleave_geglu(block=16)
+// -- a value block and its gate block are two accumulators of one lane at the same positions --, bf16 rows staged through LDS for
+// 16-byte stores.
 #include "kernels.h"
 #include <type_traits>
 
@@ -53,7 +56,7 @@ __device__ __forceinline__ f32x2 gelu2(f32x2 g) {
     return 0.5f * g * (1.0f + ys);
 }
 
-// gelu_fast_f of common.h on two values at once (round 4): x * sigmoid(x * poly(x^2)), 5 packed + 3 x 2 scalar instructions per pair
+// gelu_fast_f of common.h on two values at once (round 4): x * sigmoid(x * poly(x^2)), 6 packed + 3 x 2 scalar instructions per pair
 // instead of 12 packed + 4 x 2 scalar
 __device__ __forceinline__ f32x2 gelu2_fast(f32x2 g) {
     const f32x2 xc = {__builtin_amdgcn_fmed3f(g[0], -7.0f, 7.0f), __builtin_amdgcn_fmed3f(g[1], -7.0f, 7.0f)};
@@ -61,7 +64,8 @@ __device__ __forceinline__ f32x2 gelu2_fast(f32x2 g) {
     f32x2 pl = u * 1.01426305e-03f + -1.06775724e-01f;
     pl = pl * u + -2.30112133f;
     const f32x2 a = xc * pl;
-    const f32x2 d = {1.0f + __builtin_amdgcn_exp2f(a[0]), 1.0f + __builtin_amdgcn_exp2f(a[1])};
+    const f32x2 e = {__builtin_amdgcn_exp2f(a[0]), __builtin_amdgcn_exp2f(a[1])};
+    const f32x2 d = e + 1.0f;   // one v_pk_add_f32
     const f32x2 r = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
     return g * r;
 }
@@ -85,7 +89,7 @@ __global__ __launch_bounds__(512, 2) void geglu_big_kernel(const GemmArgsN<NP> p
     BIG_TL(tl_start);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
-    const int half = lane >> 5, l31 = lane & 31;
+    const int quad = lane >> 4, l15 = lane & 15;
 
     const int tiles_m = p.M / BM, tiles_n = p.N / BN;
     int tile_m, tile_n;   // workgroup -> tile: see gemm.hip (XCD-aware partition chosen on the host)
@@ -120,69 +124,75 @@ __global__ __launch_bounds__(512, 2) void geglu_big_kernel(const GemmArgsN<NP> p
         if (q < A_LOADS) glds16(a_base + (size_t)kt * 128 + a_off[q], smem + soff + (q * 512 + wave * 64) * 16);
         else glds16(w_base + (size_t)kt * 128 + w_off[q - A_LOADS], smem + soff + A_BYTES + ((q - A_LOADS) * 512 + wave * 64) * 16);
     };
-    // ---- fragment addresses: A row wm*64 + i*32 + l31, W row wn*160 + j*32 + l31; K slice ks = logical chunk 4*half + ks of the
-    // 128-byte row for both operands (any permutation of k inside the step is fine as long as both agree)
-    const int sw = (l31 >> 1) & 7;
-    int a_frag[4], w_frag[4];
+    // ---- fragment addresses (v_mfma_f32_16x16x32: lane l holds row l & 15 of a 16-row block, k = 8 (l >> 4) .. + 7 of the 32-wide
+    // slice): A row wm*64 + i*16 + l15, W row wn*160 + j*16 + l15; K slice ks = logical chunk 4*ks + quad of the 128-byte row for both
+    // operands (any permutation of k inside the step is fine as long as both agree).  Every block starts on a multiple of 16 rows, so the
+    // swizzle term is (l15 >> 1) & 7, and each 16-lane group of a ds_read_b128 meets eight distinct 16-byte columns on both row parities:
+    // conflict-free, as the 32-row form was.
+    const int sw = (l15 >> 1) & 7;
+    int a_frag[2], w_frag[2];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-        const int c = ((4 * half + ks) ^ sw) * 16;
-        a_frag[ks] = (wm * 64 + l31) * 128 + c;
-        w_frag[ks] = A_BYTES + (wn * 160 + l31) * 128 + c;
+    for (int ks = 0; ks < 2; ++ks) {
+        const int c = ((4 * ks + quad) ^ sw) * 16;
+        a_frag[ks] = (wm * 64 + l15) * 128 + c;
+        w_frag[ks] = A_BYTES + (wn * 160 + l15) * 128 + c;
     }
 
-    // epilogue vectors of this tile's 320 columns and the LayerNorm statistics of this lane's two tokens: fetched now, used
-    // after the main loop
-    float pre_bias = 0.f, pre_cs = 0.f;
-    if (tid < BN) {
-        if (p.bias) pre_bias = p.bias[n0 + tid];
-        if (p.ln_stats) pre_cs = p.ln_colsum[n0 + tid];
-    }
-    float ln_mean[2] = {0.f, 0.f}, ln_rstd[2] = {1.f, 1.f};
-    if (p.ln_stats) {
+    f32x4 acc[4][10];   // [token block][W block]: D[channel 4 quad + r][token l15]
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int m = m0 + wm * 64 + i * 32 + l31;
-            if (p.ln_slots == 0) {   // finalised statistics: [M][2] = (mean, rstd)
-                ln_mean[i] = p.ln_stats[(size_t)m * 2];
-                ln_rstd[i] = p.ln_stats[(size_t)m * 2 + 1];
-                continue;
-            }
-            const float* st = p.ln_stats + (size_t)m * p.ln_ld * 2;   // partial (sum, sum of squares) per producer tile column
-            float sm = 0.f, sq = 0.f;
-            for (int sl = half; sl < p.ln_slots; sl += 2) {            // the two lanes of a token split the slots
-                sm += st[2 * sl];
-                sq += st[2 * sl + 1];
-            }
-            sm += __shfl_xor(sm, 32, 64);
-            sq += __shfl_xor(sq, 32, 64);
-            const float inv = 1.0f / (float)p.K;
-            const float mean = sm * inv;
-            float var = sq * inv - mean * mean;
-            var = var > 0.f ? var : 0.f;
-            ln_mean[i] = mean;
-            ln_rstd[i] = rsqrtf(var + p.ln_eps);
-        }
-    }
-
-    f32x16 acc[2][5];
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 10; ++j)
 #pragma unroll
-        for (int j = 0; j < 5; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
 
     const int nk = p.K >> 6;
 #pragma unroll
     for (int q = 0; q < LOADS; ++q) stage_one(0, 0, q);
 
+    // The epilogue vectors of this tile's 320 columns and the LayerNorm statistics of its 256 tokens go to LDS beside the ring while
+    // the first K step lands: nothing is carried in registers across the main loop.  The statistics are finalised once per token, by
+    // lane l of wave (wm, 0) for token wm*64 + l.  (Read only after the barrier that ends the main loop.)
+    float* s_bias = (float*)(smem + S * STAGE + 256);   // [BN] bias, [BN] LayerNorm column sums, [BM] (mean, rstd)
+    float* s_cs = s_bias + BN;
+    f32x2* s_ln = (f32x2*)(s_cs + BN);
+    if (tid < BN) {
+        s_bias[tid] = p.bias ? p.bias[n0 + tid] : 0.f;
+        s_cs[tid] = p.ln_stats ? p.ln_colsum[n0 + tid] : 0.f;
+    }
+    if (wn == 0) {
+        f32x2 ms = {0.f, 1.f};
+        if (p.ln_stats) {
+            const int m = m0 + wm * 64 + lane;
+            if (p.ln_slots == 0) {   // finalised statistics: [M][2] = (mean, rstd)
+                ms = {p.ln_stats[(size_t)m * 2], p.ln_stats[(size_t)m * 2 + 1]};
+            } else {
+                const float* st = p.ln_stats + (size_t)m * p.ln_ld * 2;   // partial (sum, sum of squares) per producer tile column
+                float sm0 = 0.f, sq0 = 0.f, sm1 = 0.f, sq1 = 0.f;        // even and odd slots apart: the summation order of the 32-row form
+                for (int sl = 0; sl < p.ln_slots; sl += 2) {
+                    sm0 += st[2 * sl];
+                    sq0 += st[2 * sl + 1];
+                    if (sl + 1 < p.ln_slots) {
+                        sm1 += st[2 * sl + 2];
+                        sq1 += st[2 * sl + 3];
+                    }
+                }
+                const float inv = 1.0f / (float)p.K;
+                const float mean = (sm0 + sm1) * inv;
+                float var = (sq0 + sq1) * inv - mean * mean;
+                var = var > 0.f ? var : 0.f;
+                ms = {mean, rsqrtf(var + p.ln_eps)};
+            }
+        }
+        s_ln[wm * 64 + lane] = ms;
+    }
+
     BIG_TL(tl_loop0);
     int boff = 0;   // ring slot of the tile being read
     // One K step.  The loads of step kt+1 are issued after the barrier of step kt into the other slot (free: every wave has
-    // finished step kt-1), one per tick over the first nine ticks, and awaited at the top of step kt+1.  The step is 20 ticks q = 5 ks + j:
-    // tick q runs the two MFMAs of W block (ks, j) and issues the ds_read of block q + 2 (three fragment buffers in rotation,
-    // the activation fragments of slice ks + 1 ride along at j = 2), so a fragment read has two ticks = 128 MFMA cycles of lead.
+    // finished step kt-1), one per tick over the first nine ticks, and awaited at the top of step kt+1.  The step is 20 ticks q = 10 ks + j:
+    // tick q runs the four MFMAs of W block (ks, j) and issues the ds_read of block q + 2 (three fragment buffers in rotation; the
+    // activation fragments of slice 1 ride along on ticks 2 .. 5), so a fragment read has two ticks = 128 MFMA cycles of lead.
     auto kstep = [&](const int kt, auto more_c) {
         constexpr bool MORE = decltype(more_c)::value;
         big_wait_vmcnt<0>();
@@ -190,22 +200,20 @@ __global__ __launch_bounds__(512, 2) void geglu_big_kernel(const GemmArgsN<NP> p
         asm volatile("" ::: "memory");
         const int soff = boff == 0 ? STAGE : 0;
         const char* sT = smem + boff;
-        bf16x8 wf[3], af[2][2];
-        auto read_w = [&](int q) { return *(const bf16x8*)(sT + w_frag[q / 5] + (q % 5) * 32 * 128); };
-        auto read_a = [&](int ks, int slot) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) af[slot][i] = *(const bf16x8*)(sT + a_frag[ks] + i * 32 * 128);
-        };
-        read_a(0, 0);
+        bf16x8 wf[3], af[2][4];
+        auto read_w = [&](int q) { return *(const bf16x8*)(sT + w_frag[q / 10] + (q % 10) * 16 * 128); };
+        auto read_a = [&](int ks, int i) { af[ks][i] = *(const bf16x8*)(sT + a_frag[ks] + i * 16 * 128); };
         wf[0] = read_w(0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) read_a(0, i);
         wf[1] = read_w(1);
 #pragma unroll
         for (int q = 0; q < 20; ++q) {
-            const int ks = q / 5, j = q % 5;
+            const int ks = q / 10, j = q % 10;
             if (q + 2 < 20) wf[(q + 2) % 3] = read_w(q + 2);
-            if (j == 2 && ks < 3) read_a(ks + 1, (ks + 1) & 1);
+            if (ks == 0 && j >= 2 && j < 6) read_a(1, j - 2);
 #pragma unroll
-            for (int i = 0; i < 2; ++i) acc[i][j] = SUPIR_MFMA_32x32x16(wf[q % 3], af[ks & 1][i], acc[i][j], 0, 0, 0);
+            for (int i = 0; i < 4; ++i) acc[i][j] = SUPIR_MFMA_16x16x32(wf[q % 3], af[ks][i], acc[i][j], 0, 0, 0);
             if constexpr (MORE) {
                 // 9 loads on ticks 0 .. 8: as early as the slot is free (they are awaited at the top of the next step, so the last
                 // one needs its whole latency inside this step), but not back to back (that stalls on the vector-memory path)
@@ -222,54 +230,52 @@ __global__ __launch_bounds__(512, 2) void geglu_big_kernel(const GemmArgsN<NP> p
 
     // ------------------------------------------------------------------ epilogue
 #ifdef SUPIR_G16_TIMELINE
-    asm volatile("s_nop 0" ::"v"(acc[0][0][0]), "v"(acc[1][4][15]));
+    asm volatile("s_nop 0" ::"v"(acc[0][0][0]), "v"(acc[3][9][3]));
 #endif
     BIG_TL(tl_loop1);
     __syncthreads();   // the ring is reused: every wave is done with its last fragment reads
-    float* s_bias = (float*)smem;   // [BN] bias, [BN] LayerNorm column sums, then one staging block per wave
-    float* s_cs = s_bias + BN;
-    if (tid < BN) {
-        s_bias[tid] = pre_bias;
-        s_cs[tid] = pre_cs;
+    char* c_stage = smem + wave * (64 * C_RS);
+    // the statistics of this lane's four tokens l15 + 16 i
+    float mu[4], rs[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const f32x2 ms = s_ln[wm * 64 + i * 16 + l15];
+        mu[i] = ms[0];
+        rs[i] = ms[1];
     }
-    __syncthreads();
-    char* c_stage = smem + 4096 + wave * (32 * C_RS);
-    // D[channel][token]: lane owns token l31 and, per 32-row block of W' (= 16 value rows, then their 16 gate rows), the value
-    // channels 4*half + 8*rg + 0..3 in registers 4*rg + e and their gates in registers 8 + 4*rg + e
+    // Lane: token l15 of each 16-token block i; W block 2 g = 16 value rows, block 2 g + 1 = their 16 gate rows, so value channels
+    // 16 g + 4 quad + e sit in acc[i][2 g][e] and their gates in acc[i][2 g + 1][e].  Group-outer: the four bias and column-sum
+    // vectors of a group are read once for the four token blocks.
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const float mu = ln_mean[i], rs = ln_rstd[i];
+    for (int g = 0; g < 5; ++g) {
+        const int nl = wn * 160 + g * 32 + 4 * quad;   // value rows nl.., gate rows nl + 16..
+        const f32x4 bv = *(const f32x4*)(s_bias + nl), bg = *(const f32x4*)(s_bias + nl + 16);
+        const f32x4 cv = *(const f32x4*)(s_cs + nl), cg = *(const f32x4*)(s_cs + nl + 16);
 #pragma unroll
-        for (int j = 0; j < 5; ++j) {
+        for (int i = 0; i < 4; ++i) {
+            f32x2 r[2];
 #pragma unroll
-            for (int rg = 0; rg < 2; ++rg) {
-                const int nl = wn * 160 + j * 32 + 8 * rg + 4 * half;   // value rows nl.., gate rows nl + 16..
-                const f32x4 bv = *(const f32x4*)(s_bias + nl), bg = *(const f32x4*)(s_bias + nl + 16);
-                const f32x4 cv = *(const f32x4*)(s_cs + nl), cg = *(const f32x4*)(s_cs + nl + 16);
-                f32x2 r[2];
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const f32x2 av = {acc[i][j][4 * rg + 2 * e], acc[i][j][4 * rg + 2 * e + 1]};
-                    const f32x2 ag = {acc[i][j][8 + 4 * rg + 2 * e], acc[i][j][8 + 4 * rg + 2 * e + 1]};
-                    const f32x2 cv2 = {cv[2 * e], cv[2 * e + 1]}, cg2 = {cg[2 * e], cg[2 * e + 1]};
-                    const f32x2 bv2 = {bv[2 * e], bv[2 * e + 1]}, bg2 = {bg[2 * e], bg[2 * e + 1]};
-                    const f32x2 v = rs * (av - mu * cv2) + bv2;
-                    const f32x2 g = rs * (ag - mu * cg2) + bg2;
-                    r[e] = v * (FASTGELU ? gelu2_fast(g) : gelu2(g));
-                }
-                const u32x2 o = {f2bf_pk(r[0][0], r[0][1]), f2bf_pk(r[1][0], r[1][1])};
-                *(u32x2*)(c_stage + l31 * C_RS + (j * 16 + 8 * rg + 4 * half) * 2) = o;
+            for (int e = 0; e < 2; ++e) {
+                const f32x2 av = {acc[i][2 * g][2 * e], acc[i][2 * g][2 * e + 1]};
+                const f32x2 ag = {acc[i][2 * g + 1][2 * e], acc[i][2 * g + 1][2 * e + 1]};
+                const f32x2 cv2 = {cv[2 * e], cv[2 * e + 1]}, cg2 = {cg[2 * e], cg[2 * e + 1]};
+                const f32x2 bv2 = {bv[2 * e], bv[2 * e + 1]}, bg2 = {bg[2 * e], bg[2 * e + 1]};
+                const f32x2 v = rs[i] * (av - mu[i] * cv2) + bv2;
+                const f32x2 gt = rs[i] * (ag - mu[i] * cg2) + bg2;
+                r[e] = v * (FASTGELU ? gelu2_fast(gt) : gelu2(gt));
             }
+            const u32x2 o = {f2bf_pk(r[0][0], r[0][1]), f2bf_pk(r[1][0], r[1][1])};
+            *(u32x2*)(c_stage + (i * 16 + l15) * C_RS + (g * 16 + 4 * quad) * 2) = o;
         }
-        // the wave's 32 tokens x 80 output channels, row-major in LDS: 10 lanes x 16 B cover one row
-        const int row_base = m0 + wm * 64 + i * 32, col_base = (n0 >> 1) + wn * 80;
+    }
+    // the wave's 64 tokens x 80 output channels, row-major in LDS: 10 lanes x 16 B cover one row, 640 pieces = 10 per lane
+    {
+        const int row_base = m0 + wm * 64, col_base = (n0 >> 1) + wn * 80;
 #pragma unroll
-        for (int rr = 0; rr < 6; ++rr) {
-            const int row = rr * 6 + lane / 10, ch = lane % 10;
-            if (lane < 60 && row < 32) {
-                const f32x4 piece = *(const f32x4*)(c_stage + row * C_RS + ch * 16);
-                supir_store16((bf16_t*)p.C + (size_t)(row_base + row) * p.ldc + col_base + ch * 8, piece);
-            }
+        for (int rr = 0; rr < 10; ++rr) {
+            const int k = rr * 64 + lane, row = k / 10, ch = k - row * 10;
+            const f32x4 piece = *(const f32x4*)(c_stage + row * C_RS + ch * 16);
+            supir_store16((bf16_t*)p.C + (size_t)(row_base + row) * p.ldc + col_base + ch * 8, piece);
         }
     }
 #ifdef SUPIR_G16_TIMELINE
@@ -323,8 +329,9 @@ static int launch_big(const GemmArgs* a_in, hipStream_t st) {
         pp.p[q].gn = a.gn;
         pp.p[q].order = a.order;
     }
-    constexpr int smem = S * STAGE + 256;   // the W ring + the prefetch scratch row; the epilogue reuses the ring
-    static_assert(4096 + 8 * 32 * C_RS <= S * STAGE && 2 * BN * 4 <= 4096, "epilogue scratch must fit the ring");
+    // the ring + the prefetch scratch row + bias, column sums and token statistics; the epilogue's staging reuses the ring
+    constexpr int smem = S * STAGE + 256 + (2 * BN + 2 * BM) * 4;
+    static_assert(8 * 64 * C_RS <= S * STAGE && smem <= 160 * 1024, "epilogue staging must fit the ring, and the whole must fit the CU's LDS");
     static bool attr_set = false;
     if (!attr_set) {
         if (supir_note_hip_status(hipFuncSetAttribute((const void*)geglu_big_kernel<NP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem)) != SUPIR_OK)
