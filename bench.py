@@ -8,8 +8,12 @@ random-init SDXL + SUPIR-control weights (supir_amd.synth) and a synthetic text 
 vector [1,2816]); inputs are resident in HBM before the timed region.  One process per GPU; independent images are
 sharded one per rank (weak scaling), weights are broadcast once from rank 0 over RCCL, no collective inside a sample.
 
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line; --full then also measures everything
+else (ms per UNet step, per-kernel breakdowns and roofline with a rocprofv3 replay of the command, batched throughput, CPU baseline).
+
     python bench.py --gpus 1 --steps 2 --warmup 1
     python bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs DIR     # + DIR/samples.npy: the last timed step's images
+    python bench.py --gpus 1 --steps 2 --warmup 1 --full                 # + every supplementary figure, full record in a side file
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 ...
 """
 import argparse
@@ -370,9 +374,8 @@ def replay_profile(args, tune_path):
         return None
     d = tempfile.mkdtemp(prefix="supir_replay_", dir="/tmp")
     cmd = [rp, "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "b", "--", sys.executable, os.path.abspath(__file__),
-           "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--extra-batch", "0", "--no-kernel-profile", "--no-replay-profile",
-           "--tune", "file", "--tune-file", tune_path, "--edm-steps", str(args.edm_steps), "--res", str(args.res),
-           "--diff-dtype", args.diff_dtype, "--save-tune", os.path.join(d, "tune_child.json")]
+           "--steps", "1", "--warmup", "1", "--tune", "file", "--tune-file", tune_path, "--edm-steps", str(args.edm_steps),
+           "--res", str(args.res), "--diff-dtype", args.diff_dtype]
     env = dict(os.environ, TMPDIR="/tmp")
     try:
         subprocess.run(cmd, timeout=420, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, cwd="/tmp", env=env, check=True)
@@ -518,7 +521,7 @@ def main():
     ap.add_argument("--images-per-gpu", type=int, default=1,
                     help="images batched into one batchify_sample call per rank (test.py runs 1; >1 raises M of every GEMM)")
     ap.add_argument("--extra-batch", type=int, default=4,
-                    help="after the timed region also report throughput with this many images per call (0 = skip)")
+                    help="with --full: after the timed region also report throughput with this many images per call (0 = skip)")
     ap.add_argument("--diff-dtype", choices=["bf16", "fp16"], default="bf16",
                     help="element type of the UNet + control kernels: bf16 = BASELINE configs[1] (the metric); fp16 = the reference's "
                          "default diff_dtype, on the fp16 build of the kernels (reported in `dtype`, never the headline line)")
@@ -528,16 +531,22 @@ def main():
                          "--tune-file / supir_amd/tune_gfx950.json as they are (what the test suite does: same kernels in every process)")
     ap.add_argument("--tune-file", default=None, help="picks to load with --tune file (e.g. the file a previous run saved)")
     ap.add_argument("--save-tune", default=None,
-                    help="where rank 0 writes the picks the timed region ran with (default: gpurun_out/tune_used.json when that directory "
-                         "exists), so that a profiler run of the same command can replay exactly these kernels (--tune file --tune-file ...)")
+                    help="where rank 0 writes the picks the timed region ran with (with --full and no path given: tune_used.json "
+                         "beside the side file of the full record, when its directory already exists), so that a profiler run of the "
+                         "same command can replay exactly these kernels (--tune file --tune-file ...)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: ms per UNet step, the per-kernel "
+                         "breakdowns and roofline (with a rocprofv3 replay of this command), batched throughput and the CPU baseline; "
+                         "the full record goes to a side file.  Without it a run only sets up, warms up, times the steps, writes "
+                         "--dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-profile", action="store_true", help="with --full: skip the per-kernel breakdowns and the roofline")
     ap.add_argument("--rank-report", action="store_true",
                     help="every rank prints one '[rank-report] {json}' line on stderr: construction / fill / broadcast seconds and GB/s, host RSS, "
                          "autotune entries changed by the sync, re-capture seconds, its own images/s (tools/scale_dryrun.sh)")
     ap.add_argument("--no-replay-profile", action="store_true",
-                    help="skip the same-box sub-step that re-runs this command (1 image) under rocprofv3 --kernel-trace --stats for the "
+                    help="with --full: skip the same-box sub-step that re-runs this command (1 image) under rocprofv3 --kernel-trace --stats for the "
                          "dominant kernel's average duration under graph replay (roofline.frac_graph_replay)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps write what the last one returned (the images of batchify_sample) as DIR/samples.npy, "
@@ -635,11 +644,11 @@ def main():
              "differ_from_shipped_file": sum(1 for k, v in ops._TUNE.items() if k in shipped[0] and shipped[0][k] != v)
              + sum(1 for k, v in ops._CHOICE.items() if k in shipped[1] and shipped[1][k] != v)}
     save_to = args.save_tune or (os.path.join(ROOT, "gpurun_out", "tune_used.json") if os.path.isdir(os.path.join(ROOT, "gpurun_out")) else None)
-    if rank == 0 and save_to and args.warmup > 0:
+    if rank == 0 and save_to and args.warmup > 0 and (args.full or args.save_tune):
         ops.save_tuning(save_to)
         picks["saved_to"] = os.path.relpath(save_to, ROOT)
     replay_tune = None
-    if rank == 0 and world == 1 and args.warmup > 0 and not args.no_replay_profile and not args.no_kernel_profile:
+    if rank == 0 and world == 1 and args.full and args.warmup > 0 and not args.no_replay_profile and not args.no_kernel_profile:
         import tempfile
         replay_tune = os.path.join(tempfile.gettempdir(), f"supir_bench_picks_{os.getpid()}.json")   # the picks the timed region runs with
         ops.save_tuning(replay_tune)
@@ -675,7 +684,7 @@ def main():
 
     # ms per UNet step (one ControlWrapper call on the CFG-doubled batch), graph replay, on this rank
     extra = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         lat = P // 8
         from supir_amd.synth import synth_tensor as st
         nb = 2 * int(c["vector"].shape[0])   # CFG-doubled batch of one call: 2 x images per call
@@ -715,7 +724,7 @@ def main():
         extra["unet_step_tflops"] = UNET_STEP_TFLOP.get(lat, 0) * (nb // 2) / (ms_unet * 1e-3) if lat in UNET_STEP_TFLOP else None
 
     roofline, breakdown = None, None
-    if rank == 0 and not args.no_kernel_profile:
+    if rank == 0 and args.full and not args.no_kernel_profile:
         agg, total_us, by_shape = kernel_profile(model, P // 8, device)
         breakdown = {k: {"launches": v["launches"], "ms": round(v["us"] / 1e3, 3),
                          "tflops": round(v["flops"] / v["us"] / 1e6, 1) if v["flops"] else None,
@@ -817,7 +826,7 @@ def main():
             extra["kernel_breakdown_vae_colorfix"] = {"error": repr(e)}
         model.model.enable_graph(not args.no_graph)
 
-    if rank == 0 and world == 1 and args.extra_batch > 1 and args.extra_batch != ipg:
+    if rank == 0 and world == 1 and args.full and args.extra_batch > 1 and args.extra_batch != ipg:
         # supplementary: same workload with several images per call (raises M of every GEMM from 2048.. to n*2048..)
         nb = args.extra_batch
         xb, cb, ub = make_inputs(nb)
@@ -831,7 +840,7 @@ def main():
         del xb
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(model, device)
         except Exception as e:  # e.g. host RAM too small for the fp32 weights
@@ -863,7 +872,7 @@ def main():
                                      "collectives_forced_on_one_rank": bool(world == 1)}
         # everything measured goes to a side file; stdout carries ONE short line (the driver keeps only a few KB of the tail, and a
         # 20 KB line left round 5 without a parsed record).  Nothing is printed after it, on either stream.
-        details = write_details(full)
+        details = write_details(full) if args.full else None
         with the_line:
             print(compact_line(full, details), flush=True)
     if dist_on:

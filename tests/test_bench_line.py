@@ -4,6 +4,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 
@@ -116,3 +118,23 @@ def test_dump_outputs_writes_float32_and_samples_under_the_cap(tmp_path):
         a, b = np.load(p1[name]), np.load(p2[name])
         assert a.dtype == np.float32 and a.ndim == 1 and 0 < a.size < t.numel() and np.array_equal(a, b)
         assert np.isin(a, t.float().reshape(-1).numpy()).all()
+
+
+@pytest.mark.gpu
+def test_a_plain_run_only_times_dumps_and_prints(tmp_path):
+    """Without --full bench.py sets up, warms up, times the steps, writes --dump-outputs and prints the line: none of the supplementary
+    legs (ms per UNet step, kernel profiles, rocprofv3 replay, batched, CPU baseline) runs, and no side file is written."""
+    import numpy as np
+    cmd = [sys.executable, bench.__file__, "--steps", "1", "--warmup", "1", "--edm-steps", "2", "--res", "512", "--tune", "file",
+           "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-4000:]
+    line = json.loads(r.stdout)
+    assert line["metric"] == "1024px 50-step EDM denoise images/sec" and line["unit"] == "images/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "bf16" and line["steps"] == 1 and line["warmup"] == 1 and line["output_finite"] is True
+    assert line["value"] > 0 and abs(line["ms_per_step"] - 1e3 / line["value"]) < 1e-3 * line["ms_per_step"]
+    assert line["roofline"] is None and line["cpu_baseline"] is None
+    for k in ("details", "ms_per_unet_step", "ms_per_unet_step_inside_the_sampler", "unet_step_tflops", "batched", "vae_colorfix_tail_ms"):
+        assert k not in line, k
+    samples = np.load(tmp_path / "out" / "samples.npy")
+    assert samples.dtype == np.float32 and samples.shape == (1, 3, 512, 512) and np.isfinite(samples).all()

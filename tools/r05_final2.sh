@@ -3,7 +3,7 @@
 set -u
 O=$PWD/gpurun_out/r05_head
 mkdir -p $O
-timeout 900 python bench.py --steps 3 --warmup 1 > $O/bench_n1.json 2> $O/bench_n1.err
+timeout 900 python bench.py --steps 3 --warmup 1 --full > $O/bench_n1.json 2> $O/bench_n1.err
 echo "bench rc=$?"; tail -c 300 $O/bench_n1.err
 cp gpurun_out/tune_used.json $O/tune_used.json 2>/dev/null
 cp gpurun_out/bench_replay_rocprofv3_kernel_stats.csv $O/bench_rocprofv3_kernel_stats.csv 2>/dev/null
