@@ -106,6 +106,15 @@ int supir_gemm_bf16(const void* A, const void* W, void* C, int M, int N, int K, 
 int supir_gemm_bf16_ex(const void* A, const void* W, void* C, int M, int N, int K, int lda, int ldc, const float* bias,
                        const void* rowbias, int ld_rowbias, int rows_per_batch, const void* residual, int ldr, int act,
                        int out_mode, float alpha, int tile, const supir_launch_hints* hints, void* stream);
+/* Dynamic control scale: supir_gemm_bf16_ex with alpha read by the kernel from `alpha`, a 4-byte fp32 DEVICE cell, when it runs -- the
+ * ZeroCrossAttn output projection x + attn(...) * control_scale (SUPIR/modules/SUPIR_v0.py:138-152) under the per-step scale of
+ * `use_linear_control_scale` (sgm/modules/diffusionmodules/sampling.py:557-559).  A graph captured once replays every step; the caller
+ * writes the cell (an ordinary device copy) between replays.  Arithmetic and tile choice are those of the float entry.  Plain GEMM with
+ * bf16 / fp16 row-major output (out_mode 0) on tiles -1, 0..6 and 32..35; anything else -> SUPIR_ERR_SHAPE.  alpha == NULL ->
+ * SUPIR_ERR_ARG before any HIP call. */
+int supir_gemm_bf16_ex_dyn(const void* A, const void* W, void* C, int M, int N, int K, int lda, int ldc, const float* bias,
+                           const void* rowbias, int ld_rowbias, int rows_per_batch, const void* residual, int ldr, int act,
+                           int out_mode, const float* alpha, int tile, const supir_launch_hints* hints, void* stream);
 
 /* supir_gemm_bf16 with LayerNorm folded in (BasicTransformerBlock, sgm/modules/attention.py:465-486: every nn.LayerNorm there
  * feeds an nn.Linear).  Two halves:
@@ -251,6 +260,21 @@ int supir_groupnorm_nhwc_parts(const void* x1, const void* x2, const void* x1raw
                                int ld1, int ld2, const float* gamma, const float* beta, float eps, int act, const void* mod_g,
                                const void* mod_b, int ldm, float control_scale, void* out, int ldo, const float* part1, int nchunk1,
                                const float* part2, int nchunk2, void* stream);
+
+/* Dynamic control scale: supir_groupnorm_nhwc / supir_groupnorm_nhwc_parts with control_scale read by the kernel from a 4-byte fp32
+ * DEVICE cell when it runs -- ZeroSFT's lerp y * cs + h_raw * (1 - cs) (SUPIR/modules/SUPIR_v0.py:91-113) under the per-step scale of
+ * `use_linear_control_scale` (sgm/modules/diffusionmodules/sampling.py:557-559): one captured graph replays every step, the caller writes
+ * the cell (an ordinary device copy) between replays.  Same arithmetic; cs == 1 skips the lerp.  The ZeroSFT form only: mod_g / mod_b
+ * are required, and the caller passes x1raw / x2raw whatever the cell will hold.  control_scale == NULL or mod_g == NULL ->
+ * SUPIR_ERR_ARG before any HIP call. */
+int supir_groupnorm_nhwc_dyn(const void* x1, const void* x2, const void* x1raw, const void* x2raw, int B, int HW, int C, int C1, int ld1,
+                             int ld2, const float* gamma, const float* beta, float eps, int act, const void* mod_g,
+                             const void* mod_b, int ldm, const float* control_scale, void* out, int ldo, float* workspace,
+                             size_t workspace_bytes, const float* given_mean_var, void* stream);
+int supir_groupnorm_nhwc_parts_dyn(const void* x1, const void* x2, const void* x1raw, const void* x2raw, int B, int HW, int C, int C1,
+                                   int ld1, int ld2, const float* gamma, const float* beta, float eps, int act, const void* mod_g,
+                                   const void* mod_b, int ldm, const float* control_scale, void* out, int ldo, const float* part1,
+                                   int nchunk1, const float* part2, int nchunk2, void* stream);
 
 /* Producer partials in `unit`-channel units (part[((b * nchunk + c) * (C / unit) + u) * 2 + {0,1}], (C / 32) % unit == 0) -> per batch
  * and group (mean, biased variance), fp32 [B][32][2] = the given_mean_var input of supir_groupnorm_nhwc.  HW = pixels per batch element.

@@ -108,6 +108,12 @@ SIGNATURES.update({
     "supir_flash_attn_d512_split": [P, P, P, P, I, I, I, I, I, I, I, F, I, P, c_size_t, P],
     "supir_groupnorm_grouped": [P, I, I, I, I, F, I, P],
 })
+# dynamic control scale: the same launches with the float control_scale / alpha replaced by a pointer to a 4-byte device cell
+SIGNATURES.update({
+    "supir_groupnorm_nhwc_dyn": [t if i != 17 else P for i, t in enumerate(SIGNATURES["supir_groupnorm_nhwc"])],
+    "supir_groupnorm_nhwc_parts_dyn": [t if i != 17 else P for i, t in enumerate(SIGNATURES["supir_groupnorm_nhwc_parts"])],
+    "supir_gemm_bf16_ex_dyn": [t if i != 16 else P for i, t in enumerate(SIGNATURES["supir_gemm_bf16_ex"])],
+})
 
 # entry points that return a byte count (size_t) instead of a status
 SIZE_SIGNATURES = {"supir_flash_attn_d512_workspace": [I, I, I, I]}

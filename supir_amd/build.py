@@ -12,7 +12,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["gemm.hip", "gemm16.hip", "gemm_big.hip", "attention.hip", "xattn.hip", "attention_d512.hip", "norm.hip", "edge.hip", "sampler.hip", "api.hip"]
-HEADERS = ["common.h", "kernels.h", os.path.join("..", "..", "include", "supir_hip.h")]
+HEADERS = ["common.h", "kernels.h", "gemm_bf16_body.inc", "gemm16_body.inc", "gn_apply_body.inc",
+           os.path.join("..", "..", "include", "supir_hip.h")]
 LIB = os.path.join(HERE, "libsupir_hip.so")
 LIB_F16 = os.path.join(HERE, "libsupir_hip_f16.so")
 LIB_F32 = os.path.join(HERE, "libsupir_hip_f32.so")

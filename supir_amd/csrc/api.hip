@@ -73,6 +73,27 @@ int supir_gemm_bf16_ex(const void* A, const void* W, void* C, int M, int N, int 
     return supir_gemm_launch(a, false, (hipStream_t)stream, tile);
 }
 
+// supir_gemm_bf16_ex with alpha read from a 4-byte device cell by the kernel (include/supir_hip.h): the ZeroCrossAttn output projection
+// under a per-step control scale (SUPIR_v0.py:138-152, sampling.py:557-559).  Same validation, same tile, same arithmetic.
+int supir_gemm_bf16_ex_dyn(const void* A, const void* W, void* C, int M, int N, int K, int lda, int ldc, const float* bias,
+                           const void* rowbias, int ld_rowbias, int rows_per_batch, const void* residual, int ldr, int act,
+                           int out_mode, const float* alpha, int tile, const supir_launch_hints* hints, void* stream) {
+    if (!alpha) return SUPIR_ERR_ARG;
+    if (!A || !W || !C) return SUPIR_ERR_ARG;
+    if (act < 0 || act > SUPIR_ACT_GEGLU_ERF || out_mode < 0 || out_mode > 2 || tile > 45 || tile == 36 || tile == 41 || tile == 43 || tile == 44) return SUPIR_ERR_ARG;
+    if ((rowbias || out_mode == 2) && rows_per_batch <= 0) return SUPIR_ERR_ARG;
+    GemmArgs a{};
+    a.A = (const bf16_t*)A; a.Wt = (const bf16_t*)W; a.C = C;
+    a.bias = bias; a.rowbias = (const bf16_t*)rowbias; a.res = (const bf16_t*)residual;
+    a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldc = ldc; a.ldr = ldr; a.ld_rb = ld_rowbias;
+    a.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : M;
+    set_act(a, act); a.out_mode = out_mode; a.alpha = 0.0f;   // (the kernel loads alpha from the cell)
+    if (out_mode != 2 && (ldc % 4 != 0 || (residual && ldr % 4 != 0) || (rowbias && ld_rowbias % 4 != 0)))
+        return SUPIR_ERR_SHAPE;
+    if (const int rc = apply_hints(a, hints)) return rc;
+    return supir_gemm_launch(a, false, (hipStream_t)stream, tile, alpha);
+}
+
 int supir_gemm_bf16(const void* A, const void* W, void* C, int M, int N, int K, int lda, int ldc, const float* bias,
                     const void* rowbias, int ld_rowbias, int rows_per_batch, const void* residual, int ldr, int act,
                     int out_mode, float alpha, int tile, void* stream) {
@@ -305,6 +326,42 @@ int supir_groupnorm_nhwc_parts(const void* x1, const void* x2, const void* x1raw
     a.B = B; a.HW = HW; a.C = C; a.C1 = C1; a.ld1 = ld1; a.ld2 = ld2; a.ldm = ldm; a.ldo = ldo;
     a.act = act; a.eps = eps; a.cscale = control_scale;
     return supir_groupnorm_launch(a, (hipStream_t)stream);
+}
+
+// The two entries above with control_scale read from a 4-byte device cell by the kernel (include/supir_hip.h): ZeroSFT
+// (SUPIR_v0.py:91-113) under a per-step control scale (sampling.py:557-559).  ZeroSFT form only (mod_g / mod_b given).
+int supir_groupnorm_nhwc_dyn(const void* x1, const void* x2, const void* x1raw, const void* x2raw, int B, int HW, int C, int C1, int ld1,
+                             int ld2, const float* gamma, const float* beta, float eps, int act, const void* mod_g,
+                             const void* mod_b, int ldm, const float* control_scale, void* out, int ldo, float* workspace,
+                             size_t workspace_bytes, const float* given_mean_var, void* stream) {
+    if (!control_scale || !mod_g) return SUPIR_ERR_ARG;
+    if (!x1 || !gamma || !beta || !out || !workspace) return SUPIR_ERR_ARG;
+    if (C1 <= 0 || C1 > C) return SUPIR_ERR_ARG;
+    if (workspace_bytes < (size_t)B * 1024 * 64 * sizeof(float)) return SUPIR_ERR_ARG;
+    GnArgs a{};
+    a.x1 = (const bf16_t*)x1; a.x2 = (const bf16_t*)x2; a.x1raw = (const bf16_t*)x1raw; a.x2raw = (const bf16_t*)x2raw;
+    a.partial = workspace; a.gamma = gamma; a.beta = beta; a.given = given_mean_var;
+    a.mod_g = (const bf16_t*)mod_g; a.mod_b = (const bf16_t*)mod_b; a.out = (bf16_t*)out;
+    a.B = B; a.HW = HW; a.C = C; a.C1 = C1; a.ld1 = ld1; a.ld2 = ld2; a.ldm = ldm; a.ldo = ldo;
+    a.act = act; a.eps = eps; a.cscale = 1.0f;   // (the kernel loads the scale from the cell)
+    return supir_groupnorm_cs_launch(a, control_scale, (hipStream_t)stream);
+}
+
+int supir_groupnorm_nhwc_parts_dyn(const void* x1, const void* x2, const void* x1raw, const void* x2raw, int B, int HW, int C, int C1,
+                                   int ld1, int ld2, const float* gamma, const float* beta, float eps, int act, const void* mod_g,
+                                   const void* mod_b, int ldm, const float* control_scale, void* out, int ldo, const float* part1,
+                                   int nchunk1, const float* part2, int nchunk2, void* stream) {
+    if (!control_scale || !mod_g) return SUPIR_ERR_ARG;
+    if (!x1 || !gamma || !beta || !out || !part1) return SUPIR_ERR_ARG;
+    if (C1 <= 0 || C1 > C) return SUPIR_ERR_ARG;
+    GnArgs a{};
+    a.x1 = (const bf16_t*)x1; a.x2 = (const bf16_t*)x2; a.x1raw = (const bf16_t*)x1raw; a.x2raw = (const bf16_t*)x2raw;
+    a.gamma = gamma; a.beta = beta;
+    a.part_u1 = part1; a.nch1 = nchunk1; a.part_u2 = part2; a.nch2 = nchunk2;
+    a.mod_g = (const bf16_t*)mod_g; a.mod_b = (const bf16_t*)mod_b; a.out = (bf16_t*)out;
+    a.B = B; a.HW = HW; a.C = C; a.C1 = C1; a.ld1 = ld1; a.ld2 = ld2; a.ldm = ldm; a.ldo = ldo;
+    a.act = act; a.eps = eps; a.cscale = 1.0f;
+    return supir_groupnorm_cs_launch(a, control_scale, (hipStream_t)stream);
 }
 
 int supir_layernorm(const void* x, void* y, const float* gamma, const float* beta, int rows, int C, int ldx, int ldy,

@@ -123,12 +123,14 @@ int supir_splitk_finalize_launch(const float* part, int ksplit, int M, int N, in
                                  hipStream_t st);
 int supir_groupnorm_parts_finalize_launch(const float* part, int B, int nchunk, int C, int unit, int HW, float* mean_var, hipStream_t st);
 int supir_rowstats_finalize_launch(const float* part, float* out, int M, int ld, int slots, int dim, float eps, hipStream_t st);
-int supir_gemm_launch(const GemmArgs& a, bool conv, hipStream_t st, int force_tile);
+// alpha_cell != nullptr: the dynamic-scale form -- alpha is loaded from that 4-byte device cell when the kernel runs (plain GEMM, tiles 0-6
+// and 32-35 only; anything else -> SUPIR_ERR_SHAPE)
+int supir_gemm_launch(const GemmArgs& a, bool conv, hipStream_t st, int force_tile, const float* alpha_cell = nullptr);
 // nx = XCDs this problem's tiles are spread over (8; 4 for each problem of a two-problem grouped launch)
 void supir_choose_xcd_grid(GemmArgs& a, int tiles_m, int tiles_n, double a_bytes, double w_bytes, int resweep, int wgs_per_cu, int nx = 8);
 // gemm16.hip: tiles 32 (128 x 80) / 33 (128 x 160), v_mfma_f32_16x16x32_bf16, two K groups per workgroup
 bool supir_gemm16_supported(const GemmArgs& a, int tile, bool conv);
-int supir_gemm16_launch(const GemmArgs& a, hipStream_t st, int tile, bool conv);
+int supir_gemm16_launch(const GemmArgs& a, hipStream_t st, int tile, bool conv, const float* alpha_cell = nullptr);
 int supir_gemm16_qkv_launch(const GemmArgs& a, hipStream_t st);
 // grouped forms: n (1 or 2) problems of identical shape, one launch (tiles 33 / 34 / 35 and the fused q|k|v tile)
 int supir_gemm16_launch_n(const GemmArgs* a, int n, hipStream_t st, int tile, bool conv);
@@ -163,6 +165,8 @@ int supir_softmax_rows_launch(const float* S, bf16_t* P, int rows, int T, int Tp
                               hipStream_t st);
 int supir_groupnorm_launch(GnArgs a, hipStream_t st);
 int supir_groupnorm_launch_n(const GnArgs* a, int n, hipStream_t st);   // statistics from the producers (part_u1) or given only
+// the ZeroSFT form (mod_g set) with cscale loaded from a 4-byte device cell when the kernel runs (dynamic control scale)
+int supir_groupnorm_cs_launch(GnArgs a, const float* cscale_cell, hipStream_t st);
 int supir_groupnorm_stats_launch(GnArgs a, float* sums_out, hipStream_t st);
 int supir_layernorm_launch(const bf16_t* x, bf16_t* y, const float* gamma, const float* beta, int rows, int C, int ldx,
                            int ldy, float eps, hipStream_t st);

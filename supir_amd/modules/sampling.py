@@ -23,6 +23,10 @@ FUSED_EDM_STEP = os.environ.get("SUPIR_FUSED_EDM_STEP", "1") == "1"
 # with the fused step: the network prepares the time / label embeddings of ALL steps of an image before the loop
 # (ControlWrapper.prepare_schedule) instead of recomputing them at the head of every step
 EMB_SCHEDULE = os.environ.get("SUPIR_EMB_SCHEDULE", "1") == "1"
+# with the fused Restore-EDM step and use_linear_control_scale: every step's control scale goes into the per-image schedule too
+# (ControlWrapper.prepare_schedule(..., control_scales)) and reaches the kernels through a device cell, so one captured graph serves the
+# whole image; 0 -> the scale is a float argument of every call (a graph per value)
+DYNAMIC_CONTROL_SCALE = os.environ.get("SUPIR_DYNAMIC_CONTROL_SCALE", "1") == "1"
 
 
 def append_dims(x, ndim):
@@ -274,6 +278,16 @@ class RestoreEDMSampler(BaseDiffusionSampler):
         d = (x - denoised) / append_dims(sigma_hat, x.ndim)
         return x + append_dims(next_sigma - sigma_hat, x.ndim) * d
 
+    def _linear_control_scale(self, sigma_f, control_scale, control_scale_start):
+        """The per-step scale of use_linear_control_scale (sampling.py:557-559), on the host sigma."""
+        return (sigma_f / self.sigma_max) * (control_scale_start - control_scale) + control_scale
+
+    def _control_scales(self, sf, num_sigmas, control_scale, use_linear_control_scale, control_scale_start):
+        """Every step's control scale for the per-image schedule, or None (constant scale / DYNAMIC_CONTROL_SCALE off)."""
+        if not (use_linear_control_scale and DYNAMIC_CONTROL_SCALE):
+            return None
+        return [self._linear_control_scale(sf[i], control_scale, control_scale_start) for i in range(num_sigmas - 1)]
+
     def _gamma(self, sig_f, num_sigmas):
         return min(self.s_churn / (num_sigmas - 1), 2 ** 0.5 - 1) if self.s_tmin <= sig_f <= self.s_tmax else 0.0
 
@@ -298,7 +312,7 @@ class RestoreEDMSampler(BaseDiffusionSampler):
             eps = eps_noise if eps_noise is not None else torch.randn_like(x)
             noise_mul = float(np.sqrt(sigma_hat * sigma_hat - sigma * sigma, dtype=f32))
         if use_linear_control_scale:
-            control_scale = (sigma_f / self.sigma_max) * (control_scale_start - control_scale) + control_scale
+            control_scale = self._linear_control_scale(sigma_f, control_scale, control_scale_start)
         idx, c_skip, c_out, c_in = den.host_scalars(sigma_hat)
         twice = not isinstance(self.guider, IdentityGuider)
         reps = 2 if twice else 1
@@ -330,7 +344,9 @@ class RestoreEDMSampler(BaseDiffusionSampler):
             # every step's timestep (table index) is known now: let the network prepare all its time / label embeddings at once
             f32 = np.float32
             t_all = [ctx[0].host_scalars(f32(sf[i]) * f32(self._gamma(sf[i], num_sigmas) + 1.0))[0] for i in range(num_sigmas - 1)]
-            ctx[1].prepare_schedule(t_all, cond_cat["vector"], control=cond_cat.get("control"))
+            css = self._control_scales(sf, num_sigmas, control_scale, use_linear_control_scale, control_scale_start)
+            ctx[1].prepare_schedule(t_all, cond_cat["vector"], control=cond_cat.get("control"),
+                                    **({} if css is None else {"control_scales": css}))
             sched = True
         try:
             for i in range(num_sigmas - 1):
@@ -432,15 +448,15 @@ class _TileGroups:
         return cat
 
     @staticmethod
-    def _group_schedules(net, t_all, groups, mine, cats):
+    def _group_schedules(net, t_all, groups, mine, cats, control_scales=None):
         """One per-image embedding table per group size (all tiles share the timestep; the LQ windows differ per group: no cached
-        hint).  True when prepared."""
+        hint), with the per-step control scales when given.  True when prepared."""
         seen = set()
         for gi in mine:
             k = len(groups[gi])
             if k not in seen:
                 seen.add(k)
-                net.prepare_schedule(t_all, cats[gi]["vector"])
+                net.prepare_schedule(t_all, cats[gi]["vector"], **({} if control_scales is None else {"control_scales": control_scales}))
         return True
 
     def _static_rep(self, cat, k):
@@ -569,7 +585,8 @@ class TiledRestoreEDMSampler(_TileGroups, RestoreEDMSampler):
         if mine and EMB_SCHEDULE and hasattr(ctx[1], "prepare_schedule") and "vector" in static:
             f32 = np.float32
             t_all = [ctx[0].host_scalars(f32(sf[i]) * f32(self._gamma(sf[i], num_sigmas) + 1.0))[0] for i in range(num_sigmas - 1)]
-            sched = self._group_schedules(ctx[1], t_all, groups, mine, {gi: gstat[gi][0] for gi in mine})
+            css = self._control_scales(sf, num_sigmas, control_scale, use_linear_control_scale, control_scale_start)
+            sched = self._group_schedules(ctx[1], t_all, groups, mine, {gi: gstat[gi][0] for gi in mine}, css)
         try:
             for i in range(num_sigmas - 1):
                 gamma = self._gamma(sf[i], num_sigmas)

@@ -54,15 +54,18 @@ class ZeroSFT(nn.Module):
         gb = pre if pre is not None else self.control_side(c)
         n = self.param_free_norm
         Ccat = n.num_channels
-        cs = float(control_scale)
+        # a device cell (ControlWrapper's dynamic control scale) is passed through as it is -- no host sync -- and then the raw
+        # operand is always given: the kernel decides on the loaded value whether to lerp
+        cs = control_scale if torch.is_tensor(control_scale) else float(control_scale)
+        raw = hh if (torch.is_tensor(cs) or cs != 1.0) else None
         if h_ori is not None and self.pre_concat:
             ho = to_nhwc(h_ori)
             out = ops.groupnorm(ho, n.g32(), n.b32(), n.eps, x2=hz, mod_g=gb[..., :Ccat], mod_b=gb[..., Ccat:],
-                                control_scale=cs, x2raw=hh if cs != 1.0 else None, part=gn_part_of(h_ori), part2=pz)
+                                control_scale=cs, x2raw=raw, part=gn_part_of(h_ori), part2=pz)
         else:
             assert h_ori is None, "h_ori without pre_concat is not built by LightGLVUNet"
             out = ops.groupnorm(hz, n.g32(), n.b32(), n.eps, mod_g=gb[..., :Ccat], mod_b=gb[..., Ccat:],
-                                control_scale=cs, x1raw=hh if cs != 1.0 else None, part=pz)
+                                control_scale=cs, x1raw=raw, part=pz)
         return to_nchw(out)
 
 
@@ -96,7 +99,8 @@ class ZeroCrossAttn(nn.Module):
         T, Tk = H * W, k.shape[1]
         q = ops.gemm(xn, a.to_q.w())
         o = ops.flash_attn(q, k, vt, B, a.heads, T, Tk)
-        out = ops.gemm(o, a.to_out[0].w(), a.to_out[0].b32(), residual=xh.view(B, T, C), alpha=float(control_scale))
+        alpha = control_scale if torch.is_tensor(control_scale) else float(control_scale)   # (a device cell: read by the kernel)
+        out = ops.gemm(o, a.to_out[0].w(), a.to_out[0].b32(), residual=xh.view(B, T, C), alpha=alpha)
         return to_nchw(out.view(B, H, W, C))
 
 

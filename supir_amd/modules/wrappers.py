@@ -17,9 +17,13 @@
     the first call; SUPIR_STRICT_DTYPE=1 turns it into an error).
 
 Optional hipGraph replay: one CFG-doubled step is ~1700 kernel launches issued from Python; `enable_graph()` captures
-them once per (shape, control_scale) and replays the graph on later steps (inputs copied into static buffers).
+them once per (shape, control_scale) and replays the graph on later steps (inputs copied into static buffers).  A per-step control
+scale (`use_linear_control_scale`, sampling.py:557-559) announced through prepare_schedule(..., control_scales=...) travels in a device
+cell the kernels read at run time instead: one graph per shape serves every step of the image.
 """
 import os
+
+import numpy as np
 
 import torch
 import torch.nn as nn
@@ -81,6 +85,13 @@ class ControlWrapper(nn.Module):
         self._sched = None             # the schedule prepared last; _scheds: one per batch size (same timesteps)
         self._scheds = {}
         self._sched_armed = False
+        # per-image control-scale schedule (prepare_schedule(..., control_scales) / select_step): a device table, the 4-byte cell the
+        # ZeroSFT / ZeroCrossAttn kernels read (allocated once per device: captured graphs point at it) and the fp32 host copy
+        self._cs_cell = None
+        self._cs_table = None
+        self._cs_host = None
+        self._cs_row = None
+        self._gstats = {"captures": 0, "replays": 0, "eager": 0}
 
     @property
     def effective_dtype(self):
@@ -93,7 +104,7 @@ class ControlWrapper(nn.Module):
         self.control_model = control_model
 
     # ------------------------------------------------------------------ per-image embedding schedule
-    def prepare_schedule(self, t_values, vector, control=None):
+    def prepare_schedule(self, t_values, vector, control=None, control_scales=None):
         """Called by a sampler that knows every timestep (table index) of the image it is about to sample: both networks build
         their time + label embedding projections for ALL steps now (openaimodel.UNetModel.prepare_schedule: three GEMMs per
         network per image) instead of three M = B GEMVs and ~12 elementwise launches at the head of every step.  A step then
@@ -103,7 +114,14 @@ class ControlWrapper(nn.Module):
         input_hint_block convolution of it is step-invariant too and is then computed once per image as well.
 
         One schedule per batch size may be prepared (the tiled sampler stacks k tiles per call and has a remainder group: two
-        batch sizes, same timesteps); a call is served by the schedule prepared for ITS batch."""
+        batch sizes, same timesteps); a call is served by the schedule prepared for ITS batch.
+
+        `control_scales` (optional, one per step): the per-step control scale of `use_linear_control_scale` (sampling.py:557-559).  It
+        is stored as an fp32 device table; select_step(i) copies entry i into a device cell, and an announced call passes that cell
+        to ZeroSFT / ZeroCrossAttn instead of a float, so the scale is not part of the graph key.  Float to fp32 is the rounding the
+        float argument of the kernels gets.  Shared by the schedules of every batch size (same steps)."""
+        if control_scales is not None and len(control_scales) != len(t_values):
+            raise ValueError(f"control_scales has {len(control_scales)} entries for {len(t_values)} steps")
         with torch.no_grad(), Wt.compute_dtype(self.effective_dtype):
             if self._emb_row is None or self._emb_row.device != vector.device:
                 self._emb_row = torch.zeros(1, dtype=torch.int64, device=vector.device)
@@ -118,6 +136,14 @@ class ControlWrapper(nn.Module):
             self._scheds.clear()                    # another image's timesteps: those tables are stale
         self._scheds[int(vector.shape[0])] = self._sched
         self._sched_armed = False
+        if control_scales is None:
+            self._cs_table = self._cs_host = None
+        else:
+            self._cs_host = tuple(float(v) for v in np.asarray(control_scales, dtype=np.float64).astype(np.float32))
+            if self._cs_cell is None or self._cs_cell.device != vector.device:
+                self._cs_cell = torch.ones(1, dtype=torch.float32, device=vector.device)
+            self._cs_table = torch.tensor(self._cs_host, dtype=torch.float32, device=vector.device)
+        self._cs_row = None
 
     def select_step(self, i, expect_t=None):
         """The NEXT forward call is step `i` of the prepared schedule; its `t` must be the schedule's i-th timestep (`expect_t`, when
@@ -127,11 +153,19 @@ class ControlWrapper(nn.Module):
         if expect_t is not None and int(expect_t) != self._sched[4][i]:
             raise ValueError(f"step {i} of the prepared schedule is timestep {self._sched[4][i]}, the call is for {int(expect_t)}")
         self._emb_row.copy_(self._emb_rows[i:i + 1])
+        if self._cs_table is not None:
+            self._cs_cell.copy_(self._cs_table[i:i + 1])   # an ordinary device copy, outside any graph: the kernels only load the cell
+            self._cs_row = i
         self._sched_armed = True
+
+    def graph_stats(self):
+        """Graph-mode calls since the last enable_graph(): {"captures", "replays", "eager"} (eager = calls served without a graph)."""
+        return dict(self._gstats)
 
     def end_schedule(self):
         self._sched, self._sched_armed = None, False
         self._scheds.clear()
+        self._cs_table = self._cs_host = self._cs_row = None
         for m in (self.control_model, self.diffusion_model):
             if m is not None and hasattr(m, "end_schedule"):
                 m.end_schedule()
@@ -216,6 +250,7 @@ class ControlWrapper(nn.Module):
     # ------------------------------------------------------------------ hipGraph replay
     def enable_graph(self, on=True):
         self._graph_on = bool(on)
+        self._gstats = {"captures": 0, "replays": 0, "eager": 0}
         if not on:
             self._graphs.clear()
             self._cs_miss.clear()
@@ -224,7 +259,9 @@ class ControlWrapper(nn.Module):
         ctx, vec, ctl = c["crossattn"], c["vector"], c["control"]
         # a step of a prepared embedding schedule reads its embeddings out of the per-image tables (other launches than a plain
         # call): its own graph, valid as long as the tables are the same buffers (version)
-        key = (tuple(x.shape), float(control_scale), tuple(ctx.shape), tuple(vec.shape), Wt.cdt()) + ((sched[1:3],) if sched else ())
+        # a dynamic control scale (device cell) is read by the kernels at run time: the key holds a marker instead of the value
+        cs_key = ("dynamic", control_scale.data_ptr()) if torch.is_tensor(control_scale) else float(control_scale)
+        key = (tuple(x.shape), cs_key, tuple(ctx.shape), tuple(vec.shape), Wt.cdt()) + ((sched[1:3],) if sched else ())
         g = self._graphs.get(key)
         if g is None:
             # control_scale is a launch argument baked into the captured kernels.  With use_linear_control_scale
@@ -234,6 +271,7 @@ class ControlWrapper(nn.Module):
             skey = (key[0], key[2], key[3], key[4]) + key[5:]
             self._cs_miss[skey] = self._cs_miss.get(skey, 0) + 1
             if self._cs_miss[skey] > 2:
+                self._gstats["eager"] += 1
                 return self._forward_eager(x, t, c, control_scale)
             if len(self._graphs) >= 4:
                 self._graphs.clear()
@@ -263,6 +301,7 @@ class ControlWrapper(nn.Module):
             ops.set_prefetch(None)
             g = [graph, sx, st, sc, out]
             self._graphs[key] = g
+            self._gstats["captures"] += 1
         else:
             self._cs_miss[(key[0], key[2], key[3], key[4]) + key[5:]] = 0
         graph, sx, st, sc, out = g[:5]
@@ -278,6 +317,7 @@ class ControlWrapper(nn.Module):
         st.copy_(t)
         sc.copy_(ctl)
         graph.replay()
+        self._gstats["replays"] += 1
         return out
 
     def _note_dtype(self):
@@ -309,6 +349,15 @@ class ControlWrapper(nn.Module):
         with torch.no_grad(), Wt.compute_dtype(self.effective_dtype):
             # (inside the scope: the networks keep one table per element type and look theirs up by the scope's)
             sched = self._use_schedule(kwargs, None if vec is None else int(vec.shape[0]))   # the schedule entry serving this call, or None
+            if sched is not None and self._cs_row is not None and self.effective_dtype != torch.float32 and self._cs_cell.device == x.device:
+                # a step of a control-scale schedule: the kernels read the scale out of the cell select_step filled
+                if float(np.float32(control_scale)) != self._cs_host[self._cs_row]:
+                    raise ValueError(f"step {self._cs_row} of the prepared schedule has control scale {self._cs_host[self._cs_row]}, "
+                                     f"the call passes {control_scale}")
+                control_scale = self._cs_cell
+            self._cs_row = None
             if self._graph_on and not kwargs and x.is_cuda and self.effective_dtype != torch.float32:
                 return self._forward_graph(x, t, c, control_scale, sched)
+            if self._graph_on:
+                self._gstats["eager"] += 1
             return self._forward_eager(x, t, c, control_scale, **kwargs)

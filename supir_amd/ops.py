@@ -656,9 +656,14 @@ def gemm(a, w, bias=None, *, rowbias=None, rows_per_batch=0, residual=None, act=
     """out[M,N] = alpha*act(a[M,K] @ w[N,K]^T + bias + rowbias[batch]) + residual.  act=2 (GEGLU) -> N/2 columns.
     alt16 = (w, bias) in the 16-row GEGLU interleave: lets the autotuner also try tile 34 (csrc/gemm16.hip).
     gn_part=True: returns (out, GnPart or None) -- GroupNorm statistics of `out` per batch of `rows_per_batch` rows, when the tile
-    that runs can emit them.  The element type (bf16 or fp16) is that of `a`; every 16-bit operand must share it."""
+    that runs can emit them.  The element type (bf16 or fp16) is that of `a`; every 16-bit operand must share it.
+    alpha may be a 1-element fp32 device tensor (a dynamic control scale, read by the kernel at run time: supir_gemm_bf16_ex_dyn): same
+    tile as a float alpha would get, never grouped."""
     DT = a.dtype
+    dyn = _dyn_cell(alpha, a.device)
     if DT == torch.float32:
+        if dyn:
+            raise _lib.SupirHipError("ops.gemm: the fp32 service takes a float alpha only")
         return _f32.gemm(a, w, bias, rowbias=rowbias, rows_per_batch=rows_per_batch, residual=residual, act=act, alpha=alpha, out=out,
                          out_dtype=out_dtype, gn_part=gn_part)
     lib = _lib.load(DT)
@@ -686,11 +691,21 @@ def gemm(a, w, bias=None, *, rowbias=None, rows_per_batch=0, residual=None, act=
     def wb(t):
         return (alt16[0], alt16[1]) if (t in (34, 37) and act == 2 and alt16 is not None) else (w, bias)
 
-    def launch(t, outp=None, hints=None):
+    def launch_f(t, outp=None, hints=None, alpha_f=alpha):
         wq, bq = wb(t)
         return lib.supir_gemm_bf16_ex(a.data_ptr(), wq.data_ptr(), (out if outp is None else outp).data_ptr(), M, N, K, lda, ldc,
-                                      _p(bq), _p(rowbias), ld_rb, rows_per_batch, _p(residual), ldr, _abi_act(act), om, alpha, t,
+                                      _p(bq), _p(rowbias), ld_rb, rows_per_batch, _p(residual), ldr, _abi_act(act), om, alpha_f, t,
                                       None if hints is None else _ct.byref(hints), _stream())
+
+    def launch_dyn(t, outp=None, hints=None):
+        wq, bq = wb(t)
+        return lib.supir_gemm_bf16_ex_dyn(a.data_ptr(), wq.data_ptr(), (out if outp is None else outp).data_ptr(), M, N, K, lda, ldc,
+                                          _p(bq), _p(rowbias), ld_rb, rows_per_batch, _p(residual), ldr, _abi_act(act), om,
+                                          alpha.data_ptr(), t, None if hints is None else _ct.byref(hints), _stream())
+
+    launch = launch_dyn if dyn else launch_f
+    # the autotune of a dynamic call times the float form (alpha 1): the pick is shared with float calls of the shape (same key)
+    tune_launch = (lambda t, outp=None: launch_f(t, outp, None, 1.0)) if dyn else launch
 
     inplace = residual is not None and residual.data_ptr() == out.data_ptr()
     key = ("gemm", M, N, K, act, om) + _k(DT)
@@ -699,7 +714,7 @@ def gemm(a, w, bias=None, *, rowbias=None, rows_per_batch=0, residual=None, act=
     if tile == -1:
         ok = (lda % 8 == 0 and out.data_ptr() % 16 == 0 and (residual is None or ldr % 4 == 0)
               and (rowbias is None or ld_rb % 4 == 0))
-        big_ok = alpha == 1.0 and a.data_ptr() % 16 == 0 and (alt16 is None or alt16[0].data_ptr() % 16 == 0)
+        big_ok = not dyn and alpha == 1.0 and a.data_ptr() % 16 == 0 and (alt16 is None or alt16[0].data_ptr() % 16 == 0)
         cands = _gemm_candidates(M, N, K, act, om, ldc, epilogue_ok=ok, geglu16=alt16 is not None, big_ok=big_ok)
         if inplace:
             # in-place accumulate (x += f(x)): re-launching would change the data, so the candidates are timed into a scratch
@@ -708,15 +723,16 @@ def gemm(a, w, bias=None, *, rowbias=None, rows_per_batch=0, residual=None, act=
             if tile is None:
                 if _DEFER is None:
                     scratch = _scratch_like(out)
-                    tile = _autotune(key, cands, lambda t: launch(t, scratch))
+                    tile = _autotune(key, cands, lambda t: tune_launch(t, scratch))
                 else:
                     tile = -1
         else:
-            tile = _autotune(key, cands, launch)
+            tile = _autotune(key, cands, tune_launch)
         if tile >= 32 and tile not in cands:   # a winner cached for this shape under friendlier strides / layouts
             tile = -1
         single_tile = tile
-        tile = _pair_tile(key, tile, cands)
+        if not dyn:
+            tile = _pair_tile(key, tile, cands)
     part = None
     if gn_part and om == 0 and act != 2:
         part = _gn_part_alloc(tile, M // rows_per_batch, rows_per_batch, N, a.device)
@@ -729,11 +745,21 @@ def gemm(a, w, bias=None, *, rowbias=None, rows_per_batch=0, residual=None, act=
                               lda=lda, ldc=ldc, ldr=ldr, ld_rowbias=ld_rb)
         return sh, pr
 
-    _issue(_Launch("gemm", lib, "supir_gemm_bf16", launch, key=key + (alpha, rows_per_batch, part is not None), tkey=key, tile=tile,
+    _issue(_Launch(None if dyn else "gemm", lib, "supir_gemm_bf16_ex_dyn" if dyn else "supir_gemm_bf16", launch,
+                   key=key + ("dyn" if dyn else alpha, rows_per_batch, part is not None), tkey=key, tile=tile,
                    single_tile=single_tile, cands=cands, make=make, w=w, part=part, out=out, inplace=inplace,
                    trace=("gemm", 2.0 * M * N * K, 2.0 * (M * K + N * K + M * n_out), dict(M=M, N=N, K=K, act=act, tile=tile)),
-                   keep=(a, w, bias, rowbias, residual, out, alt16, part)))
+                   keep=(a, w, bias, rowbias, residual, out, alt16, part, alpha if dyn else None)))
     return (out, part) if gn_part else out
+
+
+def _dyn_cell(v, device):
+    """True when a scale argument is a dynamic control-scale cell: a 1-element fp32 tensor on the launch's device (checked)."""
+    if not torch.is_tensor(v):
+        return False
+    if v.numel() != 1 or v.dtype != torch.float32 or v.device != device:
+        raise _lib.SupirHipError(f"dynamic scale: expected a 1-element fp32 tensor on {device}, got {tuple(v.shape)} {v.dtype} on {v.device}")
+    return True
 
 
 _TILE_BN_WN = {0: (128, 2), 1: (64, 2), 2: (128, 2), 3: (64, 2), 4: (128, 2), 5: (256, 4), 6: (128, 2), 7: (128, 2),
@@ -1321,8 +1347,13 @@ def groupnorm_stats(x):
 def groupnorm(x, gamma, beta, eps, *, silu=False, x2=None, mod_g=None, mod_b=None, control_scale=1.0, x1raw=None,
               x2raw=None, out=None, given=None, part=None, part2=None):
     """GroupNorm(32) over channels-last x (optionally the channel concat [x | x2]); see supir_groupnorm_nhwc.
-    part / part2 = GnPart of x / x2 from their producers: one launch, no statistics pass (supir_groupnorm_nhwc_parts)."""
+    part / part2 = GnPart of x / x2 from their producers: one launch, no statistics pass (supir_groupnorm_nhwc_parts).
+    control_scale may be a 1-element fp32 device tensor (a dynamic control scale, read by the kernel at run time:
+    supir_groupnorm_nhwc[_parts]_dyn; ZeroSFT form only, with the raw operands always given): never grouped."""
     DT = x.dtype
+    dyn = _dyn_cell(control_scale, x.device)
+    if dyn and (DT == torch.float32 or mod_g is None):
+        raise _lib.SupirHipError("ops.groupnorm: a dynamic control scale needs the 16-bit ZeroSFT form (mod_g / mod_b)")
     if DT == torch.float32:
         return _f32.groupnorm(x, gamma, beta, eps, silu=silu, x2=x2, mod_g=mod_g, mod_b=mod_b, control_scale=control_scale, x1raw=x1raw,
                               x2raw=x2raw, out=out, given=given)
@@ -1366,6 +1397,16 @@ def groupnorm(x, gamma, beta, eps, *, silu=False, x2=None, mod_g=None, mod_b=Non
 
     def launch(t, outp=None):
         o = out if outp is None else outp
+        if dyn and use_parts:
+            return lib.supir_groupnorm_nhwc_parts_dyn(x.data_ptr(), _p(x2), _p(x1raw), _p(x2raw), B, HW, C, C1, ld1, ld2, gamma.data_ptr(),
+                                                      beta.data_ptr(), eps, act, _p(mod_g), _p(mod_b), ldm, control_scale.data_ptr(),
+                                                      o.data_ptr(), ldo, part.buf.data_ptr(), part.nchunk,
+                                                      0 if part2 is None else part2.buf.data_ptr(), 0 if part2 is None else part2.nchunk,
+                                                      _stream())
+        if dyn:
+            return lib.supir_groupnorm_nhwc_dyn(x.data_ptr(), _p(x2), _p(x1raw), _p(x2raw), B, HW, C, C1, ld1, ld2, gamma.data_ptr(),
+                                                beta.data_ptr(), eps, act, _p(mod_g), _p(mod_b), ldm, control_scale.data_ptr(),
+                                                o.data_ptr(), ldo, ws.data_ptr(), ws.numel() * 4, _p(given), _stream())
         if use_parts:
             return lib.supir_groupnorm_nhwc_parts(x.data_ptr(), _p(x2), _p(x1raw), _p(x2raw), B, HW, C, C1, ld1, ld2, gamma.data_ptr(),
                                                   beta.data_ptr(), eps, act, _p(mod_g), _p(mod_b), ldm, control_scale,
@@ -1389,11 +1430,12 @@ def groupnorm(x, gamma, beta, eps, *, silu=False, x2=None, mod_g=None, mod_b=Non
     # in place (ResBlock: the second norm overwrites conv1's output): a candidate timed by the pair autotune must not be applied to
     # its own input over and over -- `inplace` sends its timing launches to a scratch output (make / launch take the override)
     inplace = any(t is not None and t.data_ptr() == out.data_ptr() for t in (x, x2, x1raw, x2raw))
-    _issue(_Launch("gn" if given is None else None, lib, "supir_groupnorm_nhwc_parts" if use_parts else "supir_groupnorm_nhwc", launch,
+    _issue(_Launch("gn" if (given is None and not dyn) else None, lib,
+                   ("supir_groupnorm_nhwc_parts" if use_parts else "supir_groupnorm_nhwc") + ("_dyn" if dyn else ""), launch,
                    key=("gn", B, HW, C, eps, act, use_parts, x2 is not None, mod_g is not None, x1raw is not None or x2raw is not None)
-                   + _k(DT), make=make, out=out, inplace=inplace,
+                   + _k(DT) + (("dyn",) if dyn else ()), make=make, out=out, inplace=inplace,
                    trace=("groupnorm", 0, 2.0 * n * (2 + (2 if mod_g is not None else 0)), dict(B=B, HW=HW, C=C, parts=use_parts)),
-                   keep=(x, x2, x1raw, x2raw, gamma, beta, mod_g, mod_b, out, ws, given, part, part2)))
+                   keep=(x, x2, x1raw, x2raw, gamma, beta, mod_g, mod_b, out, ws, given, part, part2, control_scale if dyn else None)))
     return out
 
 

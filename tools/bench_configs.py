@@ -8,8 +8,11 @@ the matrix peak (algorithmic TFLOP of BASELINE.md section 2 / seconds / peak).  
   config 3   4096 x 4096, TiledRestoreEDMSampler 128 / 64 (49 tiles) + tiled VAE (512 / 64), 50 steps, bf16
   config 6   4096 x 4096, TiledRestoreDPMPP2MSampler (the Lightning sampler) 128 / 64 (49 tiles) + tiled VAE, 8 steps, fp16 network;
              tile_batch 1 and 4, the fused step on / off alternating (not a BASELINE.json entry: config 5's sampler at config 3's size)
+  config 7   linear Stage-2 guidance (`use_linear_control_scale`, control scale 1.0 from 0.0) at config 2's settings (1024 x 1024, 50 EDM
+             steps): SUPIR_DYNAMIC_CONTROL_SCALE on / off alternating, with the constant-scale image beside them
+  config 8   the same pair at config 3's settings (4096 x 4096 tiled, tile batch --tile-batch, --tiled-steps steps)
 
-Usage: python tools/bench_configs.py [--configs 1,5,3,6] [--tiled-steps 50] [--tile-batch 4] [--lightning-steps 8] [--ab-reps 3]
+Usage: python tools/bench_configs.py [--configs 1,5,3,6,7,8] [--tiled-steps 50] [--tile-batch 4] [--lightning-steps 8] [--ab-reps 3]
        [--out FILE.json]"""
 import argparse
 import json
@@ -212,5 +215,57 @@ if 6 in want:
             peak_mem_GB=round(torch.cuda.max_memory_allocated() / 1e9, 1))
         print(json.dumps(res), flush=True)
     m.model.dtype = torch.bfloat16
+
+
+def linear_cs_ab(x, reps, **kw):
+    """Seconds per image of linear Stage-2 guidance with the dynamic control scale on / off (alternating `reps` times), and of the
+    constant-scale image, after one warm-up image of each kind (autotune, graph capture)."""
+    from supir_amd.modules import sampling
+    lin = dict(kw, use_linear_control_scale=True, control_scale=1.0, control_scale_start=0.0)
+    times = {"dynamic": [], "float": [], "constant": []}
+    outs = {}
+
+    def timed(name, a):
+        torch.cuda.synchronize()
+        t0 = time.time()
+        outs[name] = m.batchify_sample(x, **a)
+        torch.cuda.synchronize()
+        return time.time() - t0
+
+    for name, flag, a in (("dynamic", True, lin), ("float", False, lin), ("constant", True, kw)):
+        sampling.DYNAMIC_CONTROL_SCALE = flag
+        timed(name, a)
+    for _ in range(reps):
+        for name, flag, a in (("dynamic", True, lin), ("float", False, lin), ("constant", True, kw)):
+            sampling.DYNAMIC_CONTROL_SCALE = flag
+            times[name].append(round(timed(name, a), 4))
+    sampling.DYNAMIC_CONTROL_SCALE = True
+    med = {k: statistics.median(v) for k, v in times.items()}
+    return dict(s_per_image=times, median=med, spread={k: round(max(v) - min(v), 4) for k, v in times.items()},
+                linear_dynamic_vs_constant=round(med["dynamic"] / med["constant"] - 1, 4),
+                linear_float_vs_constant=round(med["float"] / med["constant"] - 1, 4),
+                dynamic_equals_float_bitwise=bool(torch.equal(outs["dynamic"], outs["float"])),
+                finite=bool(all(torch.isfinite(o).all() for o in outs.values())))
+
+
+if 7 in want:
+    m.sampler_config["target"] = "sgm.modules.diffusionmodules.sampling.RestoreEDMSampler"
+    x7 = synth_tensor("img1024", (1, 3, 1024, 1024), scale=0.5).clamp(-1, 1).to(dev)
+    res["config7_1024px_50steps_linear_control_scale_ab"] = linear_cs_ab(
+        x7, args.ab_reps, cond=cond(), num_steps=50, restoration_scale=-1, s_churn=5, s_noise=1.01, cfg_scale=4.0, seed=1234,
+        color_fix_type="Wavelet", use_linear_CFG=True, cfg_scale_start=1.0)
+    print(json.dumps(res), flush=True)
+if 8 in want:
+    m.sampler_config["target"] = "sgm.modules.diffusionmodules.sampling.TiledRestoreEDMSampler"
+    m.sampler_config["params"].update(tile_size=128, tile_stride=64, tile_batch=args.tile_batch)
+    m.sampler_config["params"].pop("eta", None)
+    if not hasattr(m.first_stage_model.decoder, "original_forward"):
+        m.init_tile_vae(encoder_tile_size=512, decoder_tile_size=64)
+    R = args.tiled_res
+    x8 = synth_tensor(f"img{R}", (1, 3, R, R), scale=0.5).clamp(-1, 1).to(dev)
+    res[f"config8_{R}px_tiled_{args.tiled_steps}steps_linear_control_scale_ab"] = dict(linear_cs_ab(
+        x8, args.ab_reps, cond=cond(), num_steps=args.tiled_steps, restoration_scale=-1, s_churn=5, s_noise=1.01, cfg_scale=4.0, seed=1234,
+        color_fix_type="Wavelet", use_linear_CFG=True, cfg_scale_start=1.0), tile_batch=args.tile_batch)
+    print(json.dumps(res), flush=True)
 os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
 json.dump(res, open(args.out, "w"), indent=1)
