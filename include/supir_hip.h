@@ -384,6 +384,23 @@ int supir_dpmpp2m_step_post_tiles(const float* net_out, const float* x, const fl
                                   float cfg_scale, float m1, float m2, float m3, float m4, float noise_mul, float s_noise, float* x_next,
                                   float* den_out, const int* tile_hw, int k, int b, int C, int Hc, int Wc, int T, int reps, void* stream);
 
+/* Per-tile ("local") prompts on the tiled samplers (SUPIRModel.prepare_condition, SUPIR/models/SUPIR_model.py:168-178, turns a list of
+ * captions into a list of per-tile conditionings; both tiled samplers take `cond` as that list,
+ * sgm/modules/diffusionmodules/sampling.py:609-616, 636-643, 671-680, 705-708).  The text K / V^T of every tile are step independent:
+ * they are computed once per image into a bank, and before a network call the rows of the call's tiles are copied into the buffers the
+ * captured graph reads.  supir_gather_segments does all those copies in ONE launch: `table` = DEVICE array of n_segments entries,
+ * segment s copies `bytes` bytes from `src` to `dst` with 16-byte loads and stores.  Every dst, src and bytes must be a multiple of 16
+ * and the segments must not overlap (the table is device memory: that is the caller's contract, not checked here).
+ * max_segment_bytes = the largest `bytes` of the table (host value, a multiple of 16; it sizes the grid -- a smaller value is still
+ * correct, only slower).  n_segments <= 65535.  Allocates nothing.  NULL table, n_segments <= 0, max_segment_bytes == 0 or not a
+ * multiple of 16, or a table that is not 8-byte aligned: SUPIR_ERR_ARG before any HIP call. */
+typedef struct supir_segment {
+    void* dst;
+    const void* src;
+    size_t bytes;
+} supir_segment;
+int supir_gather_segments(const supir_segment* table, int n_segments, size_t max_segment_bytes, void* stream);
+
 /* Touch one dword per 128-byte line of [p, p+bytes) (a weight matrix) so that it is in flight through the memory-side
  * cache before the kernel that consumes it starts; launched a few ops ahead on a separate stream. `sink`: any 4 writable
  * device bytes (never written in practice). No reference counterpart: the reference re-reads fp32 weights through

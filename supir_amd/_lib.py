@@ -54,6 +54,8 @@ SIGNATURES = {
     "supir_dpmpp2m_step_post": [P, P, P, P, F, F, F, F, F, F, F, F, F, P, P, L, I, P],
     # ... x_next, den_out, tile_hw (host int[2k]), k, b, C, Hc, Wc, T, reps, stream
     "supir_dpmpp2m_step_post_tiles": [P, P, P, P, F, F, F, F, F, F, F, F, F, P, P, P, I, I, I, I, I, I, I, P],
+    # table (device array of (dst, src, bytes)), n_segments, max_segment_bytes, stream
+    "supir_gather_segments": [P, I, c_size_t, P],
     "supir_gemm_tile_for": [I, I, I],
     "supir_prefetch": [P, c_size_t, P, P],
     "supir_groupnorm_nhwc_parts": [P, P, P, P, I, I, I, I, I, I, P, P, F, I, P, P, I, F, P, I, P, I, P, I, P],

@@ -470,6 +470,12 @@ int supir_dpmpp2m_step_post_tiles(const float* net_out, const float* x, const fl
                                            tl, b, C, Hc, Wc, T, reps, (hipStream_t)stream);
 }
 
+int supir_gather_segments(const supir_segment* table, int n_segments, size_t max_segment_bytes, void* stream) {
+    if (!table || n_segments <= 0 || max_segment_bytes == 0 || (max_segment_bytes & 15) || ((uintptr_t)table & 7)) return SUPIR_ERR_ARG;
+    static_assert(sizeof(supir_segment) == sizeof(SupirSegment), "supir_segment is the kernel's table entry");
+    return supir_gather_segments_launch((const SupirSegment*)table, n_segments, max_segment_bytes, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------------------------------------------- grouped launches
 static void pack_common(GemmArgs& a, const supir_gemm_shape& sh, const supir_gemm_problem& q) {
     a.A = (const bf16_t*)q.A; a.Wt = (const bf16_t*)q.W; a.C = q.C; a.C2 = q.C2;

@@ -201,6 +201,13 @@ int supir_dpmpp2m_post_launch(const float* net_out, const float* x, const float*
 int supir_dpmpp2m_post_tiles_launch(const float* net_out, const float* x, const float* old, const float* eps, float c_out, float c_skip,
                                     float cfg, float m1, float m2, float m3, float m4, float noise_mul, float s_noise, float* x_next,
                                     float* den_out, const SupirTileList& tl, int b, int C, int Hc, int Wc, int T, int reps, hipStream_t st);
+// sampler.hip: one launch that copies n (dst, src, bytes) segments listed in a DEVICE table (supir_gather_segments)
+struct SupirSegment {
+    void* dst;
+    const void* src;
+    size_t bytes;
+};
+int supir_gather_segments_launch(const SupirSegment* table, int n_segments, size_t max_bytes, hipStream_t st);
 int supir_prefetch_launch(const void* p, size_t bytes, void* sink, hipStream_t st);
 int supir_resample_u8_launch(const uint8_t* src, uint8_t* dst_u8, float* dst_f32, const float* lut, const int* bounds, const int* kk,
                              int ksize, int in_h, int in_w, int out_h, int out_w, int ch, int vertical, hipStream_t st);

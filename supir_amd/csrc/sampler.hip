@@ -206,7 +206,30 @@ __global__ __launch_bounds__(256) void dpmpp_post_tiles_kernel(const float* __re
                    c_skip, cfg, m1, m2, m3, m4, noise_mul, s_noise, x_next[dst], den_out[dst]);
 }
 
+// Per-tile prompts (SUPIRModel.prepare_condition, SUPIR/models/SUPIR_model.py:168-178 -> the tiled samplers' list `cond`,
+// sampling.py:609-616, 636-643, 671-680, 705-708): the text K / V^T of every tile are computed once per image into a bank; before a
+// network call the rows of the call's tiles move from the bank into the buffers the captured graph reads.  One launch for all segments:
+// blockIdx.y = segment, the blocks of a row stride over its 16-byte units.  `bytes` of a segment is a multiple of 16 (the host builds the
+// table); a segment shorter than the longest one leaves its surplus blocks idle.
+__global__ __launch_bounds__(256) void gather_segments_kernel(const SupirSegment* __restrict__ table) {
+    const SupirSegment s = table[blockIdx.y];
+    const u32x4* __restrict__ src = (const u32x4*)s.src;
+    u32x4* __restrict__ dst = (u32x4*)s.dst;
+    const size_t units = s.bytes >> 4, stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < units; i += stride) dst[i] = src[i];
+}
+
 }  // namespace
+
+int supir_gather_segments_launch(const SupirSegment* table, int n_segments, size_t max_bytes, hipStream_t st) {
+    if (n_segments <= 0 || n_segments > 65535 || max_bytes == 0) return SUPIR_ERR_ARG;
+    if (((uintptr_t)table & 7) || (max_bytes & 15)) return SUPIR_ERR_SHAPE;
+    // four 16-byte units per thread up to 64 blocks per segment; longer segments loop
+    size_t gx = (max_bytes / 16 + 1023) / 1024;
+    gx = gx < 1 ? 1 : (gx > 64 ? 64 : gx);
+    SUPIR_LAUNCH(gather_segments_kernel, dim3((unsigned)gx, (unsigned)n_segments), dim3(256), 0, st, table);
+    return SUPIR_LAUNCH_STATUS();
+}
 
 int supir_edm_pre_tiles_launch(const float* x, const float* eps, float s_noise, float noise_mul, float c_in, float* x_hat, float* net_in,
                                const SupirTileList& tl, int b, int C, int Hc, int Wc, int T, int reps, hipStream_t st) {

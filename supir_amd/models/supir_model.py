@@ -146,9 +146,9 @@ class SUPIRModel(nn.Module):
         if cond is None:
             assert len(x) == len(p)   # SUPIR_model.py:95
         if cond is not None:
-            c, uc = dict(cond[0]), dict(cond[1])
-            c["control"] = _z
-            uc["control"] = _z
+            # (c a list: per-tile conditionings, as prepare_condition returns them for local prompts)
+            c = [dict(cj, control=_z) for cj in cond[0]] if isinstance(cond[0], (list, tuple)) else dict(cond[0], control=_z)
+            uc = dict(cond[1], control=_z)
         else:
             c, uc = self.prepare_condition(_z, p, p_p, n_p, N)
         denoiser = lambda inp, sigma, cc, cs: self.denoiser(self.model, inp, sigma, cc, cs, **kwargs)

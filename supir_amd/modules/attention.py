@@ -70,6 +70,33 @@ class CrossAttention(nn.Module):
         cache[key] = (context, context._version, wk, wv, k, vt)
         return k, vt
 
+    def context_kv_bank(self, contexts):
+        """K [n,Tk,C] and V^T [n,C,Tpad] of n contexts [n,Tk,Dc] in NEW tensors (not the per-shape buffers of _context_kv): the
+        per-image bank of the tiled samplers' per-tile prompts (ControlWrapper.prepare_context_bank)."""
+        ctx = tokens_bf16(contexts)
+        n, Tk, _ = ctx.shape
+        return ops.gemm(ctx, self.to_k.w()), ops.gemm_t(ctx, self.to_v.w(), None, n, Tk, _pad64(Tk))
+
+    def resident_kv(self, shape, device):
+        """The (K, V^T) buffers _context_kv keeps for contexts of `shape` in the current element type, or None."""
+        c = (self._kv_cache or {}).get((tuple(shape), device) + ops._k(cdt()))
+        return None if c is None else (c[4], c[5])
+
+    def claim_context(self, context):
+        """The buffers for contexts of this shape were just filled with the K / V^T of `context` from outside (supir_gather_segments
+        out of a bank this layer computed): _context_kv(context) returns them as they are."""
+        key = (tuple(context.shape), context.device) + ops._k(cdt())
+        c = self._kv_cache[key]
+        self._kv_cache[key] = (context, context._version) + tuple(c[2:])
+
+    def forget_context(self, shape, device):
+        """The buffers for contexts of `shape` were written from outside (supir_gather_segments): they no longer hold the context
+        _context_kv saw last, so its next call of this shape recomputes whatever tensor it is given."""
+        key = (tuple(shape), device) + ops._k(cdt())
+        c = (self._kv_cache or {}).get(key)
+        if c is not None:
+            self._kv_cache[key] = (None, -1) + tuple(c[2:])
+
     def attend(self, x, context=None, residual=None, alpha=1.0, inplace=False):
         """x [B,T,C] bf16 tokens -> to_out(attention) (* alpha) (+ residual); inplace writes into `residual`."""
         B, T, C = x.shape

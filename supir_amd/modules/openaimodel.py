@@ -252,10 +252,21 @@ class UNetModel(nn.Module):
 
         One table per (batch, element type, device), allocated at a CAPACITY of rows (>= 64): a caller that alternates step counts
         or serves several batch sizes at once (the tiled sampler's full and remainder tile groups) keeps every table -- and with it
-        every captured graph, whose key carries the table's version -- alive; the version changes on real reallocations only."""
-        n, B = len(t_values), y.shape[0]
+        every captured graph, whose key carries the table's version -- alive; the version changes on real reallocations only.
+
+        `y` may be a list of G label vectors of one shape (the tiled samplers with per-tile prompts: every tile group of a batch size has
+        its own `vector`): the table then holds G blocks of n rows, group g's step i at row g * n + i -- what the caller writes into
+        `row`.  A single tensor is G = 1."""
+        ys = list(y) if isinstance(y, (list, tuple)) else [y]
+        y = ys[0]
+        assert all(v.shape == y.shape and v.device == y.device for v in ys)
+        n, B = len(t_values) * len(ys), y.shape[0]
         t = torch.tensor(list(t_values), dtype=torch.int64, device=y.device)
-        emb = self._time_emb(t)[:, None, :] + self._label(y)[None, :, :]             # [n, B, 1280] fp32
+        te = self._time_emb(t)[:, None, :]
+        if len(ys) == 1:
+            emb = te + self._label(y)[None, :, :]                                    # [n, B, 1280] fp32
+        else:   # _label refreshes ONE buffer per shape in place: each group's sum is taken before the next label lands in it
+            emb = torch.cat([te + self._label(v)[None, :, :] for v in ys], 0)
         proj_all, blocks, offs = self._emb_project(emb.reshape(n * B, -1))
         key = (B, cdt(), y.device)
         sch = self._schedules.get(key)
@@ -314,6 +325,11 @@ class UNetModel(nn.Module):
             if isinstance(m, BasicTransformerBlock) and not m.attn2.is_self:
                 m.attn2._context_kv(context)
         self._label(y)
+
+    def text_attentions(self):
+        """The text cross-attention layers, in module order (what refresh_static_conditioning walks)."""
+        from .attention import BasicTransformerBlock
+        return [m.attn2 for m in self.modules() if isinstance(m, BasicTransformerBlock) and not m.attn2.is_self]
 
     def _conv_in(self, x, add=None):
         c = self.input_blocks[0][0]

@@ -296,7 +296,7 @@ class RestoreEDMSampler(BaseDiffusionSampler):
         return _fused_ctx(self.guider, denoiser, x)
 
     def _fused_step(self, ctx, sigma_f, next_sigma_f, x, gamma, x_center, eps_noise, control_scale, use_linear_control_scale,
-                    control_scale_start, cond_cat, sched_row=None, tiles=None):
+                    control_scale_start, cond_cat, sched_row=None, tiles=None, sched_group=None):
         """sampler_step (sampling.py:548-570) with every sigma-derived factor evaluated on the host in fp32, in the reference's
         operation order, and the tensor work in supir_edm_step_pre / _post.  Same RNG consumption as the generic path.
         tiles = (windows, T): x / eps_noise are whole canvases and the step runs on the k stacked T x T windows of them
@@ -322,7 +322,9 @@ class RestoreEDMSampler(BaseDiffusionSampler):
                                                    self.s_noise, noise_mul, c_in, reps)
         else:
             x_hat, net_in = ops.edm_step_pre(x, None if eps is None else eps.float().contiguous(), self.s_noise, noise_mul, c_in, reps)
-        if sched_row is not None:
+        if sched_row is not None and sched_group is not None:
+            net.select_step(sched_row, idx, group=sched_group, batch=net_in.shape[0])   # its group's block of the table (per-tile prompts)
+        elif sched_row is not None:
             net.select_step(sched_row, idx)     # this call's timestep embeddings come out of the per-image table (ControlWrapper.prepare_schedule)
         out = net(net_in, den.idx_tensor(idx, net_in.shape[0], x.device), cond_cat, control_scale)
         cfg = _host_cfg(self.guider, sigma_hat)
@@ -398,8 +400,11 @@ class _TileGroups:
     """What the two tiled samplers share around their per-tile step: tile batching (`tile_batch`), tile-parallel ranks
     (`tile_parallel`, `process_group`), the normalising count canvas and the repeated conditioning of a group of stacked tiles."""
 
-    def _init_tiling(self, tile_size, tile_stride, tile_batch, tile_parallel, process_group):
+    def _init_tiling(self, tile_size, tile_stride, tile_batch, tile_parallel, process_group, tile_batch_local_prompts=False):
         self.tile_size, self.tile_stride = tile_size, tile_stride
+        # per-tile ("local") prompts, `cond` as a list (sampling.py:609-616, 671-680): one tile per network call unless this is set;
+        # then `tile_batch` applies to them too and a call mixes the prompts of its tiles along the batch axis
+        self.tile_batch_local_prompts = bool(tile_batch_local_prompts)
         # SURVEY 8(f).1: with `tile_parallel` and an initialised torch.distributed group, the tile groups of a step are dealt
         # round-robin to the ranks (one process per GPU); every rank blends its own tiles into a zero canvas and ONE all-reduce
         # (sum, RCCL) of that canvas per step assembles x_next -- the only exchange the algorithm needs (the normalising
@@ -439,18 +444,38 @@ class _TileGroups:
             count[:, :, hi:he, wi:we] += tile_weights
         return count
 
-    def _group_cat(self, static, lq, grp):
-        """The conditioning of one network call on the stacked tiles grp: repeated text / vector halves + the stacked LQ windows."""
+    def _group_batch(self, use_local_prompt):
+        """Tiles per network call: `tile_batch`, for per-tile prompts only with `tile_batch_local_prompts`."""
+        return self.tile_batch if (not use_local_prompt or self.tile_batch_local_prompts) else 1
+
+    def _group_cat(self, static, lq, grp, j0=None):
+        """The conditioning of one network call on the stacked tiles grp: repeated text / vector halves + the stacked LQ windows.
+        j0 = index of the group's first tile when `static` is the LIST of per-tile conditionings (local prompts)."""
         k = len(grp)
         ctl = _stack(lq, grp)
-        cat = self._static_rep(static, k) if k > 1 else dict(static)
+        if j0 is not None:
+            cat = self._static_local(static, j0, k) if k > 1 else dict(static[j0])
+        else:
+            cat = self._static_rep(static, k) if k > 1 else dict(static)
         cat["control"] = torch.cat((ctl, ctl), 0) if not isinstance(self.guider, IdentityGuider) else ctl
         return cat
 
     @staticmethod
-    def _group_schedules(net, t_all, groups, mine, cats, control_scales=None):
+    def _group_schedules(net, t_all, groups, mine, cats, control_scales=None, local=False):
         """One per-image embedding table per group size (all tiles share the timestep; the LQ windows differ per group: no cached
-        hint), with the per-step control scales when given.  True when prepared."""
+        hint), with the per-step control scales when given.  True when prepared.  local (per-tile prompts: every group has its own
+        `vector`): the table of a group size holds one block of rows per group of that size, and the result maps a group's index to
+        its block -- what the step passes to select_step(i, group=...)."""
+        if local:
+            kw = {} if control_scales is None else {"control_scales": control_scales}
+            by_k, slot = {}, {}
+            for gi in mine:
+                members = by_k.setdefault(len(groups[gi]), [])
+                slot[gi] = len(members)
+                members.append(gi)
+            for members in by_k.values():
+                net.prepare_schedule(t_all, [cats[gi]["vector"] for gi in members], **kw)
+            return slot
         seen = set()
         for gi in mine:
             k = len(groups[gi])
@@ -458,6 +483,30 @@ class _TileGroups:
                 seen.add(k)
                 net.prepare_schedule(t_all, cats[gi]["vector"], **({} if control_scales is None else {"control_scales": control_scales}))
         return True
+
+    def _static_local(self, static, j0, k):
+        """The text / vector conditioning of the group of tiles j0 .. j0+k-1 with per-tile prompts: [uc]*k ; [c_j for j in the group], in
+        tile order (static[j] = [uc; c_j], or c_j alone without a guider).  Cached per group: the same tensors every step."""
+        cache = self.__dict__.setdefault("_rep_cache", {})
+        key = ("local", j0, k)
+        if key not in cache:
+            twice = not isinstance(self.guider, IdentityGuider)
+            rep = {}
+            for name, v in static[j0].items():
+                if name == "control" or not torch.is_tensor(v):
+                    continue
+                halves = [static[j][name].chunk(2, 0) if twice else (None, static[j][name]) for j in range(j0, j0 + k)]
+                rep[name] = torch.cat(([halves[0][0]] * k if twice else []) + [h[1] for h in halves], 0).contiguous()
+            cache[key] = rep
+        return dict(cache[key])
+
+    def _local_bank(self, net, conds, static, groups, mine, cats, kb):
+        """Per-tile prompts on a network that can bank the text K / V^T of every tile once per image (ControlWrapper.prepare_context_bank)."""
+        if not hasattr(net, "prepare_context_bank") or "crossattn" not in static[0]:
+            return
+        reps = 1 if isinstance(self.guider, IdentityGuider) else 2
+        net.prepare_context_bank([cj["crossattn"] for cj in conds],
+                                 [(cats[gi]["crossattn"], cats[gi]["vector"], list(range(gi * kb, gi * kb + len(groups[gi])))) for gi in mine], reps)
 
     def _static_rep(self, cat, k):
         """[uncond; cond] text / vector conditioning repeated for k stacked tiles: [uc]*k ; [c]*k (cached per k, so the
@@ -479,9 +528,10 @@ class _TileGroups:
 class TiledRestoreEDMSampler(_TileGroups, RestoreEDMSampler):
     """sampling.py:600-660: per step, every 128x128 latent tile takes a full sampler step; Gaussian-weighted blend."""
 
-    def __init__(self, tile_size=128, tile_stride=64, *args, tile_batch=1, tile_parallel=False, process_group=None, **kwargs):
+    def __init__(self, tile_size=128, tile_stride=64, *args, tile_batch=1, tile_parallel=False, process_group=None,
+                 tile_batch_local_prompts=False, **kwargs):
         super().__init__(*args, **kwargs)
-        self._init_tiling(tile_size, tile_stride, tile_batch, tile_parallel, process_group)
+        self._init_tiling(tile_size, tile_stride, tile_batch, tile_parallel, process_group, tile_batch_local_prompts)
         self.tile_weights = None
 
     def __call__(self, denoiser, x, cond, uc=None, num_steps=None, x_center=None, control_scale=1.0,
@@ -509,16 +559,17 @@ class TiledRestoreEDMSampler(_TileGroups, RestoreEDMSampler):
             static.append(cat)
         import torch.distributed as dist
         x, shared, world, rank, src = self._tile_ranks(x)
-        kb = 1 if use_local_prompt else self.tile_batch
+        kb = self._group_batch(use_local_prompt)
         ctx = None
         # the fused step's two tile kernels stack at most 64 tiles per group (SUPIR_MAX_TILES, csrc/kernels.h) and take exact T x T windows
         # inside the canvas; anything else (tile_batch > 64, a canvas smaller than a tile) runs the generic loop below
         fits = kb <= 64 and x.shape[-2] >= self.tile_size and x.shape[-1] >= self.tile_size
-        if fits and not use_local_prompt and type(self).sampler_step is RestoreEDMSampler.sampler_step and x_center is not None:
+        if fits and type(self).sampler_step is RestoreEDMSampler.sampler_step and x_center is not None:
             ctx = self._fused_ctx(denoiser, x)
         if ctx is not None:
-            return self._call_fused(ctx, x, tiles, tile_weights, lq, static[0], sf, num_sigmas, x_center, control_scale,
-                                    use_linear_control_scale, control_scale_start, kb, shared, world, rank, src)
+            return self._call_fused(ctx, x, tiles, tile_weights, lq, static if use_local_prompt else static[0], sf, num_sigmas, x_center,
+                                    control_scale, use_linear_control_scale, control_scale_start, kb, shared, world, rank, src,
+                                    conds=conds if use_local_prompt else None)
         if shared:
             count_all = self._count_canvas(x, tiles, tile_weights)
         groups, mine = self._tile_groups(tiles, kb, world, rank)
@@ -547,7 +598,7 @@ class TiledRestoreEDMSampler(_TileGroups, RestoreEDMSampler):
                                            next_sigma_f=sf[i + 1])
                     outs = [_x]
                 else:
-                    cat = self._group_cat(static[0], lq, grp)
+                    cat = self._group_cat(static, lq, grp, j0) if use_local_prompt else self._group_cat(static[0], lq, grp)
                     s_k = s_in.repeat(k)
                     _x = self.sampler_step(s_k * sigmas[i], s_k * sigmas[i + 1], denoiser, _stack(x, grp), conds[0], uc, gamma,
                                            _stack(x_center, grp), eps_noise=_stack(eps_noise, grp), control_scale=control_scale,
@@ -566,7 +617,7 @@ class TiledRestoreEDMSampler(_TileGroups, RestoreEDMSampler):
         return x
 
     def _call_fused(self, ctx, x, tiles, tile_weights, lq, static, sf, num_sigmas, x_center, control_scale, use_linear_control_scale,
-                    control_scale_start, kb, shared, world, rank, src):
+                    control_scale_start, kb, shared, world, rank, src, conds=None):
         """The loop of __call__ (sampling.py:624-659) on the fused step: per tile group ONE supir_edm_step_pre_tiles (crop of x and of
         the step's churn noise + the `pre` half), the network call -- announced to the per-image embedding schedule prepared once per
         group size, replayed from one hipGraph per group shape --, supir_edm_step_post on the stacked tiles and ONE supir_tile_blend into
@@ -580,13 +631,18 @@ class TiledRestoreEDMSampler(_TileGroups, RestoreEDMSampler):
         groups, mine = self._tile_groups(tiles, kb, world, rank)
         w64 = tile_weights[0, 0].contiguous()
         count = self._count_canvas(x, tiles, tile_weights)
-        gstat = {gi: (self._group_cat(static, lq, groups[gi]), _stack(x_center, groups[gi]).float().contiguous()) for gi in mine}
-        sched = False
-        if mine and EMB_SCHEDULE and hasattr(ctx[1], "prepare_schedule") and "vector" in static:
+        local = conds is not None      # per-tile prompts: `static` is the list of per-tile conditionings, a group's is built from its tiles'
+        gstat = {gi: (self._group_cat(static, lq, groups[gi], gi * kb if local else None), _stack(x_center, groups[gi]).float().contiguous())
+                 for gi in mine}
+        sched, slot = False, None
+        if mine and EMB_SCHEDULE and hasattr(ctx[1], "prepare_schedule") and "vector" in (static[0] if local else static):
             f32 = np.float32
             t_all = [ctx[0].host_scalars(f32(sf[i]) * f32(self._gamma(sf[i], num_sigmas) + 1.0))[0] for i in range(num_sigmas - 1)]
             css = self._control_scales(sf, num_sigmas, control_scale, use_linear_control_scale, control_scale_start)
-            sched = self._group_schedules(ctx[1], t_all, groups, mine, {gi: gstat[gi][0] for gi in mine}, css)
+            sched = self._group_schedules(ctx[1], t_all, groups, mine, {gi: gstat[gi][0] for gi in mine}, css, local=local)
+            if local:
+                sched, slot = True, sched
+                self._local_bank(ctx[1], conds, static, groups, mine, {gi: gstat[gi][0] for gi in mine}, kb)
         try:
             for i in range(num_sigmas - 1):
                 gamma = self._gamma(sf[i], num_sigmas)
@@ -597,7 +653,8 @@ class TiledRestoreEDMSampler(_TileGroups, RestoreEDMSampler):
                 for gi in mine:
                     cat, xc = gstat[gi]
                     out = self._fused_step(ctx, sf[i], sf[i + 1], x, gamma, xc, eps_noise, control_scale, use_linear_control_scale,
-                                           control_scale_start, cat, sched_row=i if sched else None, tiles=(groups[gi], T))
+                                           control_scale_start, cat, sched_row=i if sched else None, tiles=(groups[gi], T),
+                                           **({} if slot is None else {"sched_group": slot[gi]}))
                     ops.tile_blend(out, w64, x_next, groups[gi], T)
                 if shared:
                     dist.all_reduce(x_next, op=dist.ReduceOp.SUM, group=self.process_group)
@@ -743,7 +800,7 @@ class RestoreDPMPP2MSampler(BaseDiffusionSampler):
         noise_mul = float(nxt * (-2 * (self.eta * h)).expm1().neg().sqrt())
         return idx, c_skip, c_out, c_in, _host_cfg(self.guider, f32(sf[i])), m + [0.0] * (4 - len(m)), noise_mul
 
-    def _fused_step(self, ctx, st, x, old, eps, cond_cat, control_scale, sched_row=None, tiles=None):
+    def _fused_step(self, ctx, st, x, old, eps, cond_cat, control_scale, sched_row=None, tiles=None, sched_group=None):
         """sampler_step (sampling.py:429-483) as supir_edm_step_pre (no churn: x * c_in for every CFG copy), the network call and
         supir_dpmpp2m_step_post; st = _host_step(...).  old None: the first / last step's x_standard; eps None: no noise term.
         tiles = (windows, T): x / old / eps are canvases and the step runs on the k stacked windows (the _tiles kernels crop).
@@ -756,7 +813,9 @@ class RestoreDPMPP2MSampler(BaseDiffusionSampler):
             x_in, net_in = ops.edm_step_pre_tiles(x, None, tiles[0], tiles[1], self.s_noise, 0.0, c_in, reps)
         else:
             x_in, net_in = ops.edm_step_pre(x, None, self.s_noise, 0.0, c_in, reps)
-        if sched_row is not None:
+        if sched_row is not None and sched_group is not None:
+            net.select_step(sched_row, idx, group=sched_group, batch=net_in.shape[0])
+        elif sched_row is not None:
             net.select_step(sched_row, idx)
         out = net(net_in, den.idx_tensor(idx, net_in.shape[0], x.device), cond_cat, control_scale).float().contiguous()
         if old is None or not self.eta:
@@ -807,9 +866,10 @@ class TiledRestoreDPMPP2MSampler(_TileGroups, RestoreDPMPP2MSampler):
     tile_parallel / process_group as on TiledRestoreEDMSampler: k tiles per network call, tile groups dealt round robin to the ranks
     with ONE all-reduce per step (x_next and old_next stacked in one buffer); rank 0's start latent and per-step noise are broadcast."""
 
-    def __init__(self, tile_size=128, tile_stride=64, *args, tile_batch=1, tile_parallel=False, process_group=None, **kwargs):
+    def __init__(self, tile_size=128, tile_stride=64, *args, tile_batch=1, tile_parallel=False, process_group=None,
+                 tile_batch_local_prompts=False, **kwargs):
         super().__init__(*args, **kwargs)
-        self._init_tiling(tile_size, tile_stride, tile_batch, tile_parallel, process_group)
+        self._init_tiling(tile_size, tile_stride, tile_batch, tile_parallel, process_group, tile_batch_local_prompts)
 
     def __call__(self, denoiser, x, cond, uc=None, num_steps=None, control_scale=1.0, **kwargs):
         import torch.distributed as dist
@@ -825,17 +885,18 @@ class TiledRestoreDPMPP2MSampler(_TileGroups, RestoreDPMPP2MSampler):
         static = [self.guider.prepare_cond({k: v for k, v in cj.items() if k != "control"},
                                            {k: v for k, v in uc.items() if k != "control"}) for cj in conds]
         x, shared, world, rank, src = self._tile_ranks(x)
-        kb = 1 if use_local_prompt else self.tile_batch
+        kb = self._group_batch(use_local_prompt)
         groups, mine = self._tile_groups(tiles, kb, world, rank)
         count = self._count_canvas(x, tiles, tile_weights)
         noise_sampler = self.noise_sampler_cls(x, smin, smax)
         ctx = None
         # the tile kernels stack at most 64 tiles per group and take exact T x T windows inside the canvas (as for EDM)
-        if kb <= 64 and h >= self.tile_size and w >= self.tile_size and not use_local_prompt:
+        if kb <= 64 and h >= self.tile_size and w >= self.tile_size:
             ctx = self._fused_ctx(denoiser, x)
         if ctx is not None:
-            return self._call_fused_tiles(ctx, x, s_in, sigmas, num_sigmas, sf, tile_weights, count, lq, static[0], groups, mine,
-                                          noise_sampler, control_scale, shared, src)
+            return self._call_fused_tiles(ctx, x, s_in, sigmas, num_sigmas, sf, tile_weights, count, lq,
+                                          static if use_local_prompt else static[0], groups, mine, noise_sampler, control_scale, shared, src,
+                                          conds=conds if use_local_prompt else None, kb=kb)
         old = None
         for i in range(num_sigmas - 1):
             noisy = i > 0 and sf[i + 1] > 1e-14
@@ -867,7 +928,9 @@ class TiledRestoreDPMPP2MSampler(_TileGroups, RestoreDPMPP2MSampler):
                     _x, _old = self.sampler_step(None if old is None else _stack(old, grp),
                                                  None if i == 0 else s_k * sigmas[i - 1], s_k * sigmas[i], s_k * sigmas[i + 1],
                                                  denoiser, _stack(x, grp), conds[0], uc=uc, eps_noise=_stack(eps, grp),
-                                                 control_scale=control_scale, cond_cat=self._group_cat(static[0], lq, grp), last=last)
+                                                 control_scale=control_scale, last=last,
+                                                 cond_cat=self._group_cat(static, lq, grp, j0) if use_local_prompt
+                                                 else self._group_cat(static[0], lq, grp))
                     outs = list(zip(_x.chunk(k, 0), _old.chunk(k, 0)))
                 for (hi, he, wi, we), (_xt, _ot) in zip(grp, outs):
                     x_next[:, :, hi:he, wi:we] += _xt * tile_weights
@@ -879,7 +942,7 @@ class TiledRestoreDPMPP2MSampler(_TileGroups, RestoreDPMPP2MSampler):
         return x
 
     def _call_fused_tiles(self, ctx, x, s_in, sigmas, num_sigmas, sf, tile_weights, count, lq, static, groups, mine, noise_sampler,
-                          control_scale, shared, src):
+                          control_scale, shared, src, conds=None, kb=1):
         """The loop of __call__ on the fused step: per tile group ONE supir_edm_step_pre_tiles (crop of x + c_in), the network call
         (announced to the per-image embedding schedule prepared once per group size; replayed from one hipGraph per group shape when
         the network has graphs on), ONE supir_dpmpp2m_step_post_tiles (reads old / eps through the windows) and two supir_tile_blend
@@ -889,11 +952,15 @@ class TiledRestoreDPMPP2MSampler(_TileGroups, RestoreDPMPP2MSampler):
         den, net = ctx
         T = self.tile_size
         w64 = tile_weights[0, 0].contiguous()
-        cats = {gi: self._group_cat(static, lq, groups[gi]) for gi in mine}
+        local = conds is not None      # per-tile prompts: `static` is the list of per-tile conditionings
+        cats = {gi: self._group_cat(static, lq, groups[gi], gi * kb if local else None) for gi in mine}
         steps = [self._host_step(den, sf, i) for i in range(num_sigmas - 1)]
-        sched = False
-        if mine and EMB_SCHEDULE and hasattr(net, "prepare_schedule") and "vector" in static:
-            sched = self._group_schedules(net, [s[0] for s in steps], groups, mine, cats)
+        sched, slot = False, None
+        if mine and EMB_SCHEDULE and hasattr(net, "prepare_schedule") and "vector" in (static[0] if local else static):
+            sched = self._group_schedules(net, [s[0] for s in steps], groups, mine, cats, local=local)
+            if local:
+                sched, slot = True, sched
+                self._local_bank(net, conds, static, groups, mine, cats, kb)
         x = x.contiguous()
         old = None
         try:
@@ -907,7 +974,8 @@ class TiledRestoreDPMPP2MSampler(_TileGroups, RestoreDPMPP2MSampler):
                 buf = x.new_zeros((2,) + tuple(x.shape))
                 for gi in mine:
                     xn, dn = self._fused_step(ctx, steps[i], x, None if sf[i + 1] < 1e-14 else old, eps, cats[gi], control_scale,
-                                              sched_row=i if sched else None, tiles=(groups[gi], T))
+                                              sched_row=i if sched else None, tiles=(groups[gi], T),
+                                              **({} if slot is None else {"sched_group": slot[gi]}))
                     ops.tile_blend(xn, w64, buf[0], groups[gi], T)
                     ops.tile_blend(dn, w64, buf[1], groups[gi], T)
                 if shared:

@@ -43,6 +43,10 @@ def _capture_mode():
     return "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
 
 
+# per-tile prompts on the tiled samplers: text K / V^T of every tile computed once per image and moved into the graphs' buffers by one
+# gather launch per call (ControlWrapper.prepare_context_bank); 0 -> every replay recomputes them (refresh_static_conditioning)
+CONTEXT_BANK = os.environ.get("SUPIR_CONTEXT_BANK", "1") == "1"
+
 # fp16 requests run on the fp16 build of the kernels (True) or are served by bf16 with a warning (False)
 FP16_NATIVE = os.environ.get("SUPIR_FP16_NATIVE", "1") == "1"
 
@@ -85,6 +89,11 @@ class ControlWrapper(nn.Module):
         self._sched = None             # the schedule prepared last; _scheds: one per batch size (same timesteps)
         self._scheds = {}
         self._sched_armed = False
+        self._sched_groups = {}        # per batch size: the groups its schedule was prepared for (per-tile prompts; 1 otherwise)
+        self._sched_batch = None       # the batch size of the schedule prepared last
+        self._sel_group = 0            # the group select_step announced
+        # per-image bank of text K / V^T for the tiled samplers' per-tile prompts (prepare_context_bank)
+        self._bank = None
         # per-image control-scale schedule (prepare_schedule(..., control_scales) / select_step): a device table, the 4-byte cell the
         # ZeroSFT / ZeroCrossAttn kernels read (allocated once per device: captured graphs point at it) and the fp32 host copy
         self._cs_cell = None
@@ -122,19 +131,33 @@ class ControlWrapper(nn.Module):
         float argument of the kernels gets.  Shared by the schedules of every batch size (same steps)."""
         if control_scales is not None and len(control_scales) != len(t_values):
             raise ValueError(f"control_scales has {len(control_scales)} entries for {len(t_values)} steps")
+        groups = 1
+        if isinstance(vector, (list, tuple)):
+            # G groups of one batch size in ONE table (the tiled samplers with per-tile prompts: every tile group has its own vector):
+            # rows [G * S, B, N], group g's step i at row g * S + i -- select_step(i, group=g).  The LQ windows differ per group too.
+            groups, vectors, vector = len(vector), list(vector), vector[0]
+            if groups < 1 or control is not None:
+                raise ValueError("a schedule of several groups needs at least one vector and takes no cached `control` hint")
+        else:
+            vectors = vector
         with torch.no_grad(), Wt.compute_dtype(self.effective_dtype):
             if self._emb_row is None or self._emb_row.device != vector.device:
                 self._emb_row = torch.zeros(1, dtype=torch.int64, device=vector.device)
                 self._emb_rows = torch.arange(1024, dtype=torch.int64, device=vector.device)
-            assert len(t_values) <= self._emb_rows.numel()
-            v1 = self.control_model.prepare_schedule(t_values, vector, self._emb_row, control=control)
-            v2 = self.diffusion_model.prepare_schedule(t_values, vector, self._emb_row)
+            if groups * len(t_values) > self._emb_rows.numel():
+                # only the SOURCE of select_step's copy: captured graphs read the one-entry cell _emb_row, never this
+                self._emb_rows = torch.arange(groups * len(t_values), dtype=torch.int64, device=vector.device)
+            v1 = self.control_model.prepare_schedule(t_values, vectors, self._emb_row, control=control)
+            v2 = self.diffusion_model.prepare_schedule(t_values, vectors, self._emb_row)
             self.control_model.end_schedule()       # inactive until a step announces itself
             self.diffusion_model.end_schedule()
         self._sched = (len(t_values), v1, v2, self.effective_dtype, tuple(int(v) for v in t_values))
         if self._scheds and next(iter(self._scheds.values()))[4] != self._sched[4]:
             self._scheds.clear()                    # another image's timesteps: those tables are stale
+            self._sched_groups.clear()
         self._scheds[int(vector.shape[0])] = self._sched
+        self._sched_groups[int(vector.shape[0])] = groups
+        self._sched_batch = int(vector.shape[0])
         self._sched_armed = False
         if control_scales is None:
             self._cs_table = self._cs_host = None
@@ -145,14 +168,22 @@ class ControlWrapper(nn.Module):
             self._cs_table = torch.tensor(self._cs_host, dtype=torch.float32, device=vector.device)
         self._cs_row = None
 
-    def select_step(self, i, expect_t=None):
+    def select_step(self, i, expect_t=None, group=None, batch=None):
         """The NEXT forward call is step `i` of the prepared schedule; its `t` must be the schedule's i-th timestep (`expect_t`, when
-        given, is checked against it on the host)."""
-        if self._sched is None or not (0 <= i < self._sched[0]):
+        given, is checked against it on the host).  `group` = g: the call belongs to group g of a schedule prepared for several groups
+        (row g * S + i of the table); `batch` names the batch size whose schedule that is (default: the one prepared last)."""
+        ent = self._sched if batch is None else self._scheds.get(int(batch))
+        if ent is None or not (0 <= i < ent[0]):
             raise IndexError("select_step without a prepared schedule / out of range")
-        if expect_t is not None and int(expect_t) != self._sched[4][i]:
-            raise ValueError(f"step {i} of the prepared schedule is timestep {self._sched[4][i]}, the call is for {int(expect_t)}")
-        self._emb_row.copy_(self._emb_rows[i:i + 1])
+        g = 0 if group is None else int(group)
+        n_groups = self._sched_groups.get(self._sched_batch if batch is None else int(batch), 1)
+        if not (0 <= g < n_groups):
+            raise IndexError(f"group {g} of a schedule prepared for {n_groups} group(s)")
+        if expect_t is not None and int(expect_t) != ent[4][i]:
+            raise ValueError(f"step {i} of the prepared schedule is timestep {ent[4][i]}, the call is for {int(expect_t)}")
+        row = g * ent[0] + i
+        self._sel_group = g
+        self._emb_row.copy_(self._emb_rows[row:row + 1])
         if self._cs_table is not None:
             self._cs_cell.copy_(self._cs_table[i:i + 1])   # an ordinary device copy, outside any graph: the kernels only load the cell
             self._cs_row = i
@@ -166,15 +197,105 @@ class ControlWrapper(nn.Module):
         self._sched, self._sched_armed = None, False
         self._scheds.clear()
         self._cs_table = self._cs_host = self._cs_row = None
+        self._sel_group = 0
+        self._sched_groups.clear()
+        self.end_context_bank()        # bank calls are schedule calls: the image is over
         for m in (self.control_model, self.diffusion_model):
             if m is not None and hasattr(m, "end_schedule"):
                 m.end_schedule()
+
+    # ------------------------------------------------------------------ per-image text K / V^T bank (per-tile prompts)
+    def prepare_context_bank(self, tile_contexts, groups, reps):
+        """The tiled samplers with per-tile prompts (SUPIR_model.py:168-178 -> sampling.py:609-616, 671-680) call the networks with a
+        different `crossattn` tensor for every tile group, so every replay of a captured graph would first recompute the text K / V^T
+        of all cross-attention layers (refresh_static_conditioning: two GEMMs per layer, ~200 launches per call).  They are step
+        independent: compute them ONCE per image for every tile's context [1, Tk, D] into a bank, and move the rows of a call's tiles
+        into the buffers the graphs read with ONE supir_gather_segments launch before the replay.
+
+        groups = [(crossattn, vector, tile indices)]: the stacked conditioning tensors the calls will pass (identity matters) and the
+        tiles whose contexts sit in the last len(indices) rows of `crossattn` (after the unconditional rows when reps == 2).  The
+        unconditional half of a shape's buffers is written here, once.  Used by the calls a prepared embedding schedule serves (those
+        read no label embedding) -- replayed or eager, so both compute from the same K / V^T; every other call takes the ordinary
+        refresh.  Returns False (nothing prepared) for the fp32 service, off the GPU or with the switch CONTEXT_BANK off;
+        end_context_bank() releases the bank."""
+        from .. import ops
+        self.end_context_bank()
+        dev = tile_contexts[0].device
+        if not (CONTEXT_BANK and dev.type == "cuda" and self.effective_dtype != torch.float32 and groups):
+            return False
+        with torch.no_grad(), Wt.compute_dtype(self.effective_dtype):
+            layers = self.control_model.text_attentions() + self.diffusion_model.text_attentions()
+            banks = [a.context_kv_bank(torch.cat(list(tile_contexts), 0)) for a in layers]
+            shapes, tables = {}, {}
+            for ctx, vec, idx in groups:
+                if tuple(ctx.shape) not in shapes:       # creates the buffers of this shape on first use; writes their uncond rows
+                    self.control_model.refresh_static_conditioning(ctx, vec)
+                    self.diffusion_model.refresh_static_conditioning(ctx, vec)
+                    shapes[tuple(ctx.shape)] = (tuple(ctx.shape), tuple(vec.shape), Wt.cdt())
+                k = len(idx)
+                first = ctx.shape[0] - k
+                runs = [[idx[0], 1]]                      # consecutive tiles are one segment per layer and operand
+                for j in idx[1:]:
+                    if j == runs[-1][0] + runs[-1][1]:
+                        runs[-1][1] += 1
+                    else:
+                        runs.append([j, 1])
+                pairs = []
+                for a, (kb, vtb) in zip(layers, banks):
+                    rk, rvt = a.resident_kv(ctx.shape, dev)
+                    row = first
+                    for j0, n in runs:
+                        pairs += [(rk[row:row + n], kb[j0:j0 + n]), (rvt[row:row + n], vtb[j0:j0 + n])]
+                        row += n
+                tables[id(ctx)] = (ctx, ctx._version, vec, vec._version, ops.SegmentTable(pairs))
+            self._bank = {"cdt": Wt.cdt(), "tables": tables, "shapes": shapes, "layers": layers, "device": dev, "gathers": 0}
+            self._bank_forget()
+        return True
+
+    def _bank_forget(self):
+        """The buffers of the bank's shapes are written by gathers: neither the layers' own caches nor the _resident token may go on
+        claiming a context for them."""
+        b = self._bank
+        for sh, rkey in b["shapes"].items():
+            for a in b["layers"]:
+                a.forget_context(sh, b["device"])
+            self._resident.pop(rkey, None)
+
+    def _bank_apply(self, table, ctx, vec, claim):
+        """ONE launch moves the rows of this call's tiles out of the bank into the buffers of its context shape.  claim: an eager pass
+        follows (a plain call, a warm-up, a capture) -- the layers' caches are told that the buffers hold `ctx`, so it reads them
+        instead of recomputing; replays need no such bookkeeping."""
+        from .. import ops
+        ops.gather_segments(table)
+        self._bank["gathers"] += 1
+        if claim:
+            for a in self._bank["layers"]:
+                a.claim_context(ctx)
+        self._resident[(tuple(ctx.shape), tuple(vec.shape), Wt.cdt())] = (ctx, ctx._version, vec, vec._version)
+
+    def _bank_table(self, ctx, vec, sched):
+        b = self._bank
+        if b is None or sched is None or b["cdt"] != Wt.cdt():
+            return None
+        e = b["tables"].get(id(ctx))
+        if e is None or e[0] is not ctx or e[1] != ctx._version or e[2] is not vec or e[3] != vec._version:
+            return None
+        return e[4]
+
+    def end_context_bank(self):
+        if self._bank is not None:
+            with Wt.compute_dtype(self._bank["cdt"]):
+                self._bank_forget()
+            self._bank = None
 
     def _use_schedule(self, kwargs, B=None):
         """Consume the one-call announcement; switch both networks' tables (the ones prepared for batch B) on / off for this call.
         Returns the schedule entry that serves the call, or None."""
         ent = self._scheds.get(B) if B is not None else self._sched
         use = ent is not None and self._sched_armed and not kwargs and ent[3] == self.effective_dtype
+        if use and self._sel_group >= self._sched_groups.get(B, 1):
+            raise IndexError(f"the call was announced as group {self._sel_group}; the schedule for batch {B} has "
+                             f"{self._sched_groups.get(B, 1)} group(s)")
         self._sched_armed = False
         for m in (self.control_model, self.diffusion_model):
             if m is not None and hasattr(m, "use_schedule"):
@@ -263,6 +384,8 @@ class ControlWrapper(nn.Module):
         cs_key = ("dynamic", control_scale.data_ptr()) if torch.is_tensor(control_scale) else float(control_scale)
         key = (tuple(x.shape), cs_key, tuple(ctx.shape), tuple(vec.shape), Wt.cdt()) + ((sched[1:3],) if sched else ())
         g = self._graphs.get(key)
+        # a call of the per-image context bank: its K / V^T rows are gathered instead of recomputed
+        bank = self._bank_table(ctx, vec, sched)
         if g is None:
             # control_scale is a launch argument baked into the captured kernels.  With use_linear_control_scale
             # (sampling.py:557-559) it changes on every step: capturing a graph per value would cost three network calls per
@@ -272,16 +395,20 @@ class ControlWrapper(nn.Module):
             self._cs_miss[skey] = self._cs_miss.get(skey, 0) + 1
             if self._cs_miss[skey] > 2:
                 self._gstats["eager"] += 1
+                if bank is not None:
+                    self._bank_apply(bank, ctx, vec, claim=True)
                 return self._forward_eager(x, t, c, control_scale)
             if len(self._graphs) >= 4:
                 self._graphs.clear()
+            if bank is not None:
+                self._bank_apply(bank, ctx, vec, claim=True)     # the warm-up passes read the bank's rows too
             sx, st, sc = x.clone(), t.clone(), ctl.clone()
             cond = {"crossattn": ctx, "vector": vec, "control": sc}
             # warm-up on a side stream: fills the weight / text-KV / label caches OUTSIDE the capture
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             from .. import ops
-            pf = ops.WeightPrefetch(self.prefetch_distance, self.prefetch_kind) if self.prefetch_distance > 0 else None
+            pf =ops.WeightPrefetch(self.prefetch_distance, self.prefetch_kind) if self.prefetch_distance > 0 else None
             with torch.cuda.stream(s):
                 self._forward_eager(sx, st, cond, control_scale)
                 if pf is not None:            # second warm-up pass doubles as the recording pass (op order is static)
@@ -307,7 +434,11 @@ class ControlWrapper(nn.Module):
         graph, sx, st, sc, out = g[:5]
         rkey = (key[2], key[3], key[4])
         res = self._resident.get(rkey)
-        if res is None or res[0] is not ctx or res[1] != ctx._version or res[2] is not vec or res[3] != vec._version:
+        stale = res is None or res[0] is not ctx or res[1] != ctx._version or res[2] is not vec or res[3] != vec._version
+        if stale and bank is not None:
+            # (the label embedding is not read: the call's embeddings come out of the schedule's table)
+            self._bank_apply(bank, ctx, vec, claim=False)
+        elif stale:
             # the shared buffers hold another prompt's K / V^T / label embedding (a new prompt, or another graph / an eager call
             # of the same shape ran in between): refresh them in place, keep the graph
             self.control_model.refresh_static_conditioning(ctx, vec)
@@ -360,4 +491,7 @@ class ControlWrapper(nn.Module):
                 return self._forward_graph(x, t, c, control_scale, sched)
             if self._graph_on:
                 self._gstats["eager"] += 1
+            bank = self._bank_table(c.get("crossattn"), vec, sched) if isinstance(c, dict) else None
+            if bank is not None:
+                self._bank_apply(bank, c["crossattn"], vec, claim=True)
             return self._forward_eager(x, t, c, control_scale, **kwargs)

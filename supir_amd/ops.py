@@ -1606,6 +1606,45 @@ def tile_blend(out_tiles, weights, canvas, tiles, T):
     return canvas
 
 
+class SegmentTable:
+    """A device table of (dst, src, bytes) copies for gather_segments, built once and launched many times.  `pairs` = [(dst, src)]:
+    contiguous tensors (or contiguous views) of equal byte size, 16-byte aligned, a multiple of 16 bytes long; the destinations must not
+    overlap each other or any source.  The table keeps its tensors alive."""
+
+    def __init__(self, pairs):
+        if not pairs:
+            raise _lib.SupirHipError("SegmentTable: no segments")
+        rows, spans = [], []
+        for dst, src in pairs:
+            nb = dst.numel() * dst.element_size()
+            if not (dst.is_contiguous() and src.is_contiguous()) or nb != src.numel() * src.element_size() or dst.device != src.device:
+                raise _lib.SupirHipError("SegmentTable: a segment needs contiguous dst / src of equal byte size on one device")
+            if nb == 0 or (nb | dst.data_ptr() | src.data_ptr()) & 15:
+                raise _lib.SupirHipError("SegmentTable: dst, src and the byte count of a segment must be non-zero multiples of 16")
+            rows.append((dst.data_ptr(), src.data_ptr(), nb))
+            spans.append((dst.data_ptr(), dst.data_ptr() + nb, True))
+            spans.append((src.data_ptr(), src.data_ptr() + nb, False))
+        spans.sort()
+        end_any = end_dst = 0
+        for s0, s1, is_dst in spans:      # sorted by start: a span overlaps an earlier one iff it starts before that one's end
+            if s0 < (end_any if is_dst else end_dst):
+                raise _lib.SupirHipError("SegmentTable: a destination overlaps another segment")
+            end_any = max(end_any, s1)
+            end_dst = max(end_dst, s1) if is_dst else end_dst
+        self.n, self.max_bytes, self.device = len(rows), max(r[2] for r in rows), pairs[0][0].device
+        self.keep = [t for p in pairs for t in p]
+        self.table = torch.tensor(rows, dtype=torch.int64).to(self.device)      # [n, 3]: supir_segment, field for field
+
+
+def gather_segments(table):
+    """Run every copy of a SegmentTable in ONE launch on the current stream (16-byte loads and stores).  See supir_gather_segments."""
+    lib = _lib.load()
+    _check_dev(table.table)
+    _no_defer("gather_segments")
+    rc = lib.supir_gather_segments(table.table.data_ptr(), table.n, table.max_bytes, _stream())
+    _lib.check(rc, "supir_gather_segments", lib)
+
+
 def _f32c(t):
     return t if t is None or (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
 
