@@ -318,6 +318,22 @@ int supir_pointwise_nchw(const float* x, const float* w, const float* bias, floa
 int supir_wavelet_level(const float* img, float* low, float* high, int planes, int H, int W, int radius, int first,
                         void* stream);
 
+/* Fast mode of the tiled VAE (SUPIR/utils/tilevae.py:855-876): the input is down-sampled with F.interpolate(scale_factor=s,
+ * mode="nearest-exact") and its per-channel mean / std are moved back to the input's before the GroupNorm statistics are estimated on it.
+ *
+ * supir_image_moments: out [C][4] fp64 = (sum, sum of squares, min, max) per channel over (N, OH, OW) of x[n][c][iy[oy]][ix[ox]], x fp32
+ * NCHW [N][C<=8][H][W].  iy [OH] / ix [OW] are device int tables of source rows / columns (every entry inside [0, H) / [0, W); the
+ * caller builds them with the interpolation's index rule); both NULL: the whole image (then OH == H, OW == W).  fp64 accumulation in a
+ * fixed order.  workspace: at least N * C * 256 * 4 doubles. */
+int supir_image_moments(const float* x, const int* iy, const int* ix, double* out, double* workspace, size_t workspace_bytes, int N,
+                        int C, int H, int W, int OH, int OW, void* stream);
+
+/* out [N][C][OH][OW] fp32 = clamp((x[n][c][iy[oy]][ix[ox]] - mean_new) / std_new * std_old + mean_old, min(x), max(x)), evaluated in
+ * fp32 in that order; (mean, unbiased std)_old per channel from mom_old = supir_image_moments of the whole image, _new from mom_new = its
+ * moments over the same tables; min / max over all channels of mom_old.  N * OH * OW >= 2. */
+int supir_downsample_nearest_exact_affine(const float* x, const int* iy, const int* ix, float* out, const double* mom_old,
+                                          const double* mom_new, int N, int C, int H, int W, int OH, int OW, void* stream);
+
 /* One pass (vertical != 0: along y, else along x) of Pillow's 8-bit separable resampler -- what PIL.Image.resize(size, BICUBIC)
  * does inside PIL2Tensor (SUPIR/util.py:60-83; arithmetic: third-party Pillow, src/libImaging/Resample.c).  src / dst_u8 are HWC
  * uint8 with `channels` interleaved channels.  bounds [out][2] = (first input index, tap count), coeffs [out][ksize] = 22-bit

@@ -44,6 +44,10 @@ SIGNATURES = {
     "supir_wavelet_level": [P, P, P, I, I, I, I, I, P],
     "supir_resample_u8": [P, P, P, P, P, P, I, I, I, I, I, I, I, P],
     "supir_bicubic_f32": [P, P, P, I, I, I, I, I, P],
+    # x, iy, ix, out (fp64 [C][4]), workspace, workspace_bytes, N, C, H, W, OH, OW, stream
+    "supir_image_moments": [P, P, P, P, P, c_size_t, I, I, I, I, I, I, P],
+    # x, iy, ix, out, mom_old, mom_new, N, C, H, W, OH, OW, stream
+    "supir_downsample_nearest_exact_affine": [P, P, P, P, P, P, I, I, I, I, I, I, P],
     "supir_edm_step_pre": [P, P, F, F, F, P, P, L, I, P],
     "supir_edm_step_post": [P, P, P, F, F, F, F, F, F, P, L, I, P],
     # x, eps, s_noise, noise_mul, c_in, x_hat, net_in, tile_hw (host int[2k]), k, b, C, Hc, Wc, T, reps, stream

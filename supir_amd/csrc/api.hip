@@ -401,6 +401,18 @@ int supir_wavelet_level(const float* img, float* low, float* high, int planes, i
     return supir_wavelet_level_launch(img, low, high, planes, H, W, radius, first, (hipStream_t)stream);
 }
 
+int supir_image_moments(const float* x, const int* iy, const int* ix, double* out, double* workspace, size_t workspace_bytes, int N,
+                        int C, int H, int W, int OH, int OW, void* stream) {
+    if (!x || !out || !workspace) return SUPIR_ERR_ARG;
+    return supir_image_moments_launch(x, iy, ix, out, workspace, workspace_bytes, N, C, H, W, OH, OW, (hipStream_t)stream);
+}
+
+int supir_downsample_nearest_exact_affine(const float* x, const int* iy, const int* ix, float* out, const double* mom_old,
+                                          const double* mom_new, int N, int C, int H, int W, int OH, int OW, void* stream) {
+    if (!x || !iy || !ix || !out || !mom_old || !mom_new || x == out) return SUPIR_ERR_ARG;
+    return supir_downsample_affine_launch(x, iy, ix, out, mom_old, mom_new, N, C, H, W, OH, OW, (hipStream_t)stream);
+}
+
 int supir_resample_u8(const void* src, void* dst_u8, float* dst_f32, const float* lut, const int* bounds, const int* coeffs, int ksize,
                       int in_h, int in_w, int out_h, int out_w, int channels, int vertical, void* stream) {
     if (!src || !bounds || !coeffs) return SUPIR_ERR_ARG;

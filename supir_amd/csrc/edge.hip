@@ -598,3 +598,145 @@ int supir_bicubic_f32_launch(const float* src, uint8_t* out_u8, float* out_f32, 
                  (float)H / (float)OH, (float)W / (float)OW);
     return SUPIR_LAUNCH_STATUS();
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// Fast mode of the tiled VAE (SUPIR/utils/tilevae.py:855-876): the GroupNorm statistics of the whole network are estimated on a
+// nearest-exact down-sampled copy of the input whose per-channel mean / std are moved back to the input's.
+//
+// image_moments: per-channel (sum, sum of squares, min, max) of an fp32 NCHW image, or -- with the index tables iy [OH] / ix [OW] --
+// of the OH x OW pixels F.interpolate(mode="nearest-exact") would gather from it, without materialising them.  fp64 accumulation (a
+// 4096^2 plane is 16.7 M addends), wave64 shuffle reduction, one partial per workgroup, a second tiny launch adds the partials of a
+// channel over images and chunks in a fixed order (reproducible, the idiom of gn_stats_kernel / gn_finalize_kernel).
+__device__ __forceinline__ double wave_sum_f64(double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ double wave_min_f64(double v) {
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ double wave_max_f64(double v) {
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+__global__ __launch_bounds__(256) void image_moments_kernel(const float* __restrict__ x, const int* __restrict__ iy,
+                                                            const int* __restrict__ ix, double* __restrict__ partial, int H, int W,
+                                                            int OH, int OW, long per_chunk) {
+    __shared__ double red[4][4];
+    const int tid = threadIdx.x, chunk = blockIdx.x, plane = blockIdx.y;
+    const long total = (long)OH * OW;
+    const long i0 = (long)chunk * per_chunk, i1 = i0 + per_chunk < total ? i0 + per_chunk : total;
+    const float* p = x + (size_t)plane * H * W;
+    double s = 0.0, q = 0.0;
+    float mn = INFINITY, mx = -INFINITY;
+    for (long i = i0 + tid; i < i1; i += 256) {
+        float v;
+        if (ix) {
+            const int oy = (int)(i / OW), ox = (int)(i - (long)oy * OW);
+            v = p[(size_t)iy[oy] * W + ix[ox]];
+        } else {
+            v = p[i];
+        }
+        s += (double)v;
+        q += (double)v * (double)v;
+        mn = fminf(mn, v);
+        mx = fmaxf(mx, v);
+    }
+    s = wave_sum_f64(s);
+    q = wave_sum_f64(q);
+    const double dmn = wave_min_f64((double)mn), dmx = wave_max_f64((double)mx);
+    if ((tid & 63) == 0) {
+        red[tid >> 6][0] = s;
+        red[tid >> 6][1] = q;
+        red[tid >> 6][2] = dmn;
+        red[tid >> 6][3] = dmx;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double* o = partial + ((size_t)plane * gridDim.x + chunk) * 4;
+        o[0] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+        o[1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+        o[2] = fmin(fmin(red[0][2], red[1][2]), fmin(red[2][2], red[3][2]));
+        o[3] = fmax(fmax(red[0][3], red[1][3]), fmax(red[2][3], red[3][3]));
+    }
+}
+
+// out [C][4] = (sum, sum of squares, min, max) of channel c over all images: one wave per channel
+__global__ __launch_bounds__(64) void image_moments_finalize_kernel(const double* __restrict__ partial, double* __restrict__ out, int N,
+                                                                    int C, int nchunk) {
+    const int c = blockIdx.x, t = threadIdx.x;
+    double s = 0.0, q = 0.0, mn = INFINITY, mx = -INFINITY;
+    for (int n = 0; n < N; ++n)
+        for (int k = t; k < nchunk; k += 64) {
+            const double* e = partial + (((size_t)n * C + c) * nchunk + k) * 4;
+            s += e[0];
+            q += e[1];
+            mn = fmin(mn, e[2]);
+            mx = fmax(mx, e[3]);
+        }
+    s = wave_sum_f64(s);
+    q = wave_sum_f64(q);
+    mn = wave_min_f64(mn);
+    mx = wave_max_f64(mx);
+    if (t == 0) {
+        out[c * 4 + 0] = s;
+        out[c * 4 + 1] = q;
+        out[c * 4 + 2] = mn;
+        out[c * 4 + 3] = mx;
+    }
+}
+
+#define SUPIR_MOMENTS_MAX_CHUNKS 256
+
+int supir_image_moments_launch(const float* x, const int* iy, const int* ix, double* out, double* workspace, size_t workspace_bytes,
+                               int N, int C, int H, int W, int OH, int OW, hipStream_t st) {
+    if (N <= 0 || C <= 0 || C > 8 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0 || (long)N * C > 65535) return SUPIR_ERR_SHAPE;
+    if ((iy == nullptr) != (ix == nullptr)) return SUPIR_ERR_ARG;
+    if (!ix && (OH != H || OW != W)) return SUPIR_ERR_SHAPE;      // without tables the moments are the whole image's
+    const long total = (long)OH * OW;
+    long nchunk = (total + 4095) / 4096;
+    if (nchunk > SUPIR_MOMENTS_MAX_CHUNKS) nchunk = SUPIR_MOMENTS_MAX_CHUNKS;
+    const long per_chunk = (total + nchunk - 1) / nchunk;
+    if (workspace_bytes < (size_t)N * C * nchunk * 4 * sizeof(double)) return SUPIR_ERR_ARG;
+    SUPIR_LAUNCH(image_moments_kernel, dim3((unsigned)nchunk, N * C), dim3(256), 0, st, x, iy, ix, workspace, H, W, OH, OW, per_chunk);
+    SUPIR_LAUNCH(image_moments_finalize_kernel, dim3(C), dim3(64), 0, st, workspace, out, N, C, (int)nchunk);
+    return SUPIR_LAUNCH_STATUS();
+}
+
+// downsample_nearest_exact_affine: out[n][c][oy][ox] = clamp((x[n][c][iy[oy]][ix[ox]] - mean_new) / std_new * std_old + mean_old,
+// min(x), max(x)) in the reference's fp32 operation order (tilevae.py:866-872); mean / UNBIASED std per channel over (N, H, W) come
+// from the two image_moments results (mom_old: the whole image, mom_new: the gathered pixels), min / max over all channels of mom_old.
+__global__ __launch_bounds__(256) void downsample_affine_kernel(const float* __restrict__ x, const int* __restrict__ iy,
+                                                                const int* __restrict__ ix, float* __restrict__ out,
+                                                                const double* __restrict__ mom_old, const double* __restrict__ mom_new,
+                                                                int C, int H, int W, int OH, int OW, double n_old, double n_new) {
+#pragma clang fp contract(off)
+    const int ox = blockIdx.x * 256 + threadIdx.x, oy = blockIdx.y, plane = blockIdx.z, c = plane % C;
+    if (ox >= OW) return;
+    const double so = mom_old[c * 4], qo = mom_old[c * 4 + 1], sn = mom_new[c * 4], qn = mom_new[c * 4 + 1];
+    const double mo = so / n_old, mnw = sn / n_new;
+    const float mean_old = (float)mo, mean_new = (float)mnw;
+    const float std_old = (float)sqrt(fmax(qo - so * mo, 0.0) / (n_old - 1.0));
+    const float std_new = (float)sqrt(fmax(qn - sn * mnw, 0.0) / (n_new - 1.0));
+    double lo = mom_old[2], hi = mom_old[3];
+    for (int k = 1; k < C; ++k) {
+        lo = fmin(lo, mom_old[k * 4 + 2]);
+        hi = fmax(hi, mom_old[k * 4 + 3]);
+    }
+    const float v = x[((size_t)plane * H + iy[oy]) * W + ix[ox]];
+    float r = (v - mean_new) / std_new;
+    r = r * std_old;
+    r = r + mean_old;
+    r = fminf(fmaxf(r, (float)lo), (float)hi);
+    out[((size_t)plane * OH + oy) * OW + ox] = r;
+}
+
+int supir_downsample_affine_launch(const float* x, const int* iy, const int* ix, float* out, const double* mom_old, const double* mom_new,
+                                   int N, int C, int H, int W, int OH, int OW, hipStream_t st) {
+    if (N <= 0 || C <= 0 || C > 8 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0 || OH > 65535 || (long)N * C > 65535) return SUPIR_ERR_SHAPE;
+    if ((long)N * OH * OW < 2) return SUPIR_ERR_SHAPE;            // the unbiased std needs two samples
+    SUPIR_LAUNCH(downsample_affine_kernel, dim3((OW + 255) / 256, OH, N * C), dim3(256), 0, st, x, iy, ix, out, mom_old, mom_new, C, H,
+                 W, OH, OW, (double)N * H * W, (double)N * OH * OW);
+    return SUPIR_LAUNCH_STATUS();
+}

@@ -178,6 +178,12 @@ int supir_pointwise_nchw_launch(const float* x, const float* w, const float* bia
                                 long HW, float in_scale, hipStream_t st);
 int supir_wavelet_level_launch(const float* img, float* low, float* high, int planes, int H, int W, int radius, int first,
                                hipStream_t st);
+// fast mode of the tiled VAE: per-channel moments of an fp32 NCHW image (optionally of a nearest-exact gather) and the gather itself
+// with the distribution-shift repair
+int supir_image_moments_launch(const float* x, const int* iy, const int* ix, double* out, double* workspace, size_t workspace_bytes,
+                               int N, int C, int H, int W, int OH, int OW, hipStream_t st);
+int supir_downsample_affine_launch(const float* x, const int* iy, const int* ix, float* out, const double* mom_old, const double* mom_new,
+                                   int N, int C, int H, int W, int OH, int OW, hipStream_t st);
 // sampler.hip: the elementwise halves of one Restore-EDM sampler step around the network call (fp32 latents, host-side scalars)
 int supir_edm_pre_launch(const float* x, const float* eps, float s_noise, float noise_mul, float c_in, float* x_hat, float* net_in,
                          long n, int reps, hipStream_t st);

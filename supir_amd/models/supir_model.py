@@ -170,15 +170,19 @@ class SUPIRModel(nn.Module):
             return samples, dict(z=_z, x_stage1=x_stage1, z_stage1=z_stage1, samples=_samples)
         return samples
 
-    def init_tile_vae(self, encoder_tile_size=512, decoder_tile_size=64):
-        """SUPIR_model.py:138-150: route the three VAE nets through the tiled forward (test.py --use_tile_vae)."""
+    def init_tile_vae(self, encoder_tile_size=512, decoder_tile_size=64, fast_encoder=False, fast_decoder=False, color_fix=False,
+                      tile_chunk=None):
+        """SUPIR_model.py:138-150: route the three VAE nets through the tiled forward (test.py --use_tile_vae).  The reference installs
+        the hook with fast modes and color_fix off, and so do the defaults; the keywords are the hook's own (utils/tilevae.py).
+        tile_chunk bounds the tiles in flight of the nets that run in fast mode without color_fix (the others take all tiles at once)."""
         from ..utils.tilevae import VAEHook
         fs = self.first_stage_model
         for net, size, dec in ((fs.denoise_encoder, encoder_tile_size, False), (fs.encoder, encoder_tile_size, False),
                                (fs.decoder, decoder_tile_size, True)):
             net.original_forward = net.forward
-            net.forward = VAEHook(net, size, is_decoder=dec, fast_decoder=False, fast_encoder=False, color_fix=False,
-                                  to_gpu=True)
+            independent = fast_decoder if dec else (fast_encoder and not color_fix)
+            net.forward = VAEHook(net, size, is_decoder=dec, fast_decoder=fast_decoder, fast_encoder=fast_encoder, color_fix=color_fix,
+                                  to_gpu=True, tile_chunk=tile_chunk if independent else None)
 
     def prepare_condition(self, _z, p, p_p, n_p, N):
         if self.conditioner is None:

@@ -1714,3 +1714,79 @@ def wavelet_decomposition(img, levels=5, want_high=True):
         _rec("wavelet_level", 0, 4.0 * N * C * H * W * (2 + (2 if (want_high and i) else 1 if want_high else 0)), ev)
         cur = low
     return high, cur
+
+
+# --------------------------------------------------------------------------------------------- tiled VAE fast mode (utils/tilevae.py)
+def groupnorm_mean_var(x):
+    """(mean, biased variance) per (batch, group) of a channels-last tensor: fp32 [B, 32, 2], the `given` operand of `groupnorm`.
+    16-bit: the statistics launch + supir_groupnorm_parts_finalize (its sums are one chunk of C/32-channel units); fp32 service: its
+    fp64 sums, finished in fp64."""
+    B, C = x.shape[0], x.shape[-1]
+    HW = int(math.prod(x.shape[1:-1]))
+    sums = groupnorm_stats(x)
+    if x.dtype == torch.float32:
+        n = float(HW * (C // 32))
+        mean = sums[..., 0] / n
+        return torch.stack([mean, (sums[..., 1] / n - mean * mean).clamp_min(0.0)], dim=-1).float().contiguous()
+    lib = _lib.load(x.dtype)
+    out = torch.empty(B, 32, 2, dtype=torch.float32, device=x.device)
+    ev = _ev()
+    _lib.check(lib.supir_groupnorm_parts_finalize(sums.data_ptr(), B, 1, C, C // 32, HW, out.data_ptr(), _stream()),
+               "supir_groupnorm_parts_finalize", lib)
+    _rec("groupnorm_parts_finalize", 0, 8.0 * B * 32, ev, B=B, C=C, nchunk=1)
+    return out
+
+
+_MOMENTS_CHUNKS = 256      # csrc/edge.hip SUPIR_MOMENTS_MAX_CHUNKS
+
+
+def _index_table(idx, size, device):
+    """A host-built table of source rows / columns -> int32 device tensor; every entry is checked against the axis BEFORE any launch."""
+    idx = torch.as_tensor(idx, dtype=torch.int32, device="cpu").contiguous()
+    if idx.dim() != 1 or idx.numel() == 0 or int(idx.min()) < 0 or int(idx.max()) >= size:
+        raise _lib.SupirHipError(f"index table outside [0, {size})")
+    return idx.to(device)
+
+
+def image_moments(x, iy=None, ix=None):
+    """Per-channel (sum, sum of squares, min, max) over (N, H, W) of an fp32 NCHW image: fp64 [C, 4].  With the host index tables iy /
+    ix (utils.tilevae.nearest_exact_index; device int32 tensors from an earlier call are taken as they are): of the pixels
+    x[:, :, iy][:, :, :, ix] instead, without materialising them.  See supir_image_moments."""
+    lib = _lib.load()
+    _check_dev(x)
+    assert x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous() and (iy is None) == (ix is None)
+    N, C, H, W = x.shape
+    if iy is not None:
+        iy = iy if (torch.is_tensor(iy) and iy.is_cuda) else _index_table(iy, H, x.device)
+        ix = ix if (torch.is_tensor(ix) and ix.is_cuda) else _index_table(ix, W, x.device)
+    OH, OW = (H, W) if iy is None else (iy.numel(), ix.numel())
+    out = torch.empty(C, 4, dtype=torch.float64, device=x.device)
+    ws = torch.empty(N * C * _MOMENTS_CHUNKS * 4, dtype=torch.float64, device=x.device)
+    _no_defer("image_moments")
+    ev = _ev()
+    rc = lib.supir_image_moments(x.data_ptr(), _p(iy), _p(ix), out.data_ptr(), ws.data_ptr(), ws.numel() * 8, N, C, H, W, OH, OW, _stream())
+    _lib.check(rc, "supir_image_moments", lib)
+    _rec("image_moments", 0, 4.0 * N * C * OH * OW, ev)
+    return out
+
+
+def downsample_nearest_exact_affine(x, iy, ix, mom_old, mom_new):
+    """F.interpolate(x, scale_factor=s, mode="nearest-exact") as the gather x[:, :, iy][:, :, :, ix] (host index tables), then
+    (v - mean_new) / std_new * std_old + mean_old clamped to [x.min(), x.max()] (SUPIR/utils/tilevae.py:860-872): fp32 [N, C, OH, OW].
+    mom_old = image_moments(x), mom_new = image_moments(x, iy, ix).  See supir_downsample_nearest_exact_affine."""
+    lib = _lib.load()
+    _check_dev(x, mom_old, mom_new)
+    assert x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
+    N, C, H, W = x.shape
+    assert mom_old.dtype == mom_new.dtype == torch.float64 and mom_old.shape == mom_new.shape == (C, 4)
+    assert mom_old.is_contiguous() and mom_new.is_contiguous()
+    iy, ix = _index_table(iy, H, x.device), _index_table(ix, W, x.device)
+    OH, OW = iy.numel(), ix.numel()
+    out = torch.empty(N, C, OH, OW, dtype=torch.float32, device=x.device)
+    _no_defer("downsample_nearest_exact_affine")
+    ev = _ev()
+    rc = lib.supir_downsample_nearest_exact_affine(x.data_ptr(), iy.data_ptr(), ix.data_ptr(), out.data_ptr(), mom_old.data_ptr(),
+                                                   mom_new.data_ptr(), N, C, H, W, OH, OW, _stream())
+    _lib.check(rc, "supir_downsample_nearest_exact_affine", lib)
+    _rec("downsample_nearest_exact_affine", 0, 8.0 * N * C * OH * OW, ev)
+    return out
