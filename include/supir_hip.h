@@ -193,8 +193,10 @@ int supir_flash_attn_d64_ex(const void* Q, const void* K, const void* Vt, void* 
  *                              Wq the gamma-folded weight, bias the beta . Wq^T term, ln_colsum[n] = sum_k Wq[n][k]]
  *     O = softmax(q K^T * scale) V      per head of 64 channels
  * X:[B*T][ldx], Wq:[H*64][C], bias / ln_colsum:[H*64] fp32 (16-byte aligned), K:[B][Tk][ldk] and Vt:[B][H*64][ldvt] as in
- * supir_flash_attn_d64, O:[B*T][ldo].  T % 128 == 0, C % 64 == 0, C >= 192, Tk <= 128, all leading dimensions multiples of 8, all
- * pointers 16-byte aligned; anything else returns SUPIR_ERR_SHAPE and the caller issues the projection and the attention separately.
+ * supir_flash_attn_d64, O:[B*T][ldo].  T % 128 == 0, C % 64 == 0, C >= 192, any Tk >= 1 (ldvt >= roundup(Tk, 64)), all leading
+ * dimensions multiples of 8, all pointers 16-byte aligned; anything else returns SUPIR_ERR_SHAPE and the caller issues the projection
+ * and the attention separately.  Keys are taken 64 at a time: the two tiles of one 77-token prompt chunk ride in on the projection's
+ * last two steps; the tiles of a chunked long prompt (154, 231, ... tokens) stream through the same three LDS buffers behind them.
  * ln_stats / ln_ld / ln_slots as in supir_gemm_bf16_ln (ln_slots <= 64; 0 = finalized (mean, rstd) pairs).
  * q never exists in memory; it is rounded to bf16 once (after the fold, with the softmax scale and log2 e folded in), so results
  * differ from the two-launch path by that one rounding.  hints (may be NULL): next_weight only (parity tests: tests/test_kernels_gpu.py::test_xattn_q_*).

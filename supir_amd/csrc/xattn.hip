@@ -1,4 +1,5 @@
-// Fused "to_q projection + text cross-attention" for head dim 64 and a SHORT key axis (Tk <= 128: the 77 text tokens), gfx950.
+// Fused "to_q projection + text cross-attention" for head dim 64 and a text-sized key axis (the 77 text tokens of one prompt chunk, or
+// 154 / 231 / ... of a chunked long prompt: any Tk, streamed 64 keys at a time), gfx950.
 //
 // Replaces, in one launch, the pair the reference runs for every cross-attention of a BasicTransformerBlock
 // (sgm/modules/attention.py:241-249 to_q, :273-277 / :357-359 the attention itself; K / V of the text context are projected once per
@@ -9,8 +10,12 @@
 // global_load_lds ring, v_mfma_f32_32x32x16 with swapped operands so that D[channel][token] puts one token per lane), keeps it in
 // registers as the B operand of S^T = K . Q^T -- the accumulator's channel order inside a 16-wide k block is
 // [0-3, 8-11 | 4-7, 12-15] over the two lane halves, so the K fragments are read with the same permutation (two 8-byte LDS reads
-// instead of one 16-byte read): no cross-lane exchange, no q round trip through HBM -- and runs the attention over the <= 2 key tiles,
-// which arrive in the ring buffers the last two K steps no longer need.  LayerNorm fold as in supir_gemm_bf16_ln
+// instead of one 16-byte read): no cross-lane exchange, no q round trip through HBM -- and runs the attention over the key tiles.
+// Key tile t lives in ring buffer (kv0 + t) % 3: tiles 0 and 1 arrive in the buffers the last two K steps no longer need (one
+// 77-token chunk never pays more than that: no barrier and no wait inside its attention loop); tile 2 goes to the third buffer after
+// the barrier that ends the projection, and from then on every tile t >= 2 is awaited (vmcnt 0: the next-weight prefetch shares the
+// counter) and published by one workgroup barrier, which also proves every wave done with tile t - 1 and so frees the buffer of
+// tile t - 2 for tile t + 1, issued right behind it and hidden under tile t's arithmetic.  LayerNorm fold as in supir_gemm_bf16_ln
 // (q = rstd (x . W'^T - mean colsum) + b'), softmax scale folded into q.  Grid = (T / 128) x H x B workgroups of 72 KB LDS (two per CU);
 // the heads of one row block are neighbours on one XCD (its L2 keeps the 128 x C token tile they all read).
 #include "kernels.h"
@@ -191,12 +196,16 @@ __global__ __launch_bounds__(256, 2) void xattn_q_kernel(const XattnArgs p) {
     xq_wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
+    // key tile 2 (long prompts): the buffer the last K step used is free from here on; a key tile ends at +16 KB of it, under the
+    // prefetch dump at +20 KB
+    const int kv2 = buf == 0 ? XQ_S - 1 : buf - 1;
+    if (nt > 2) stage_kv(kv2, 2);
 
     // next-weight prefetch (supir_launch_hints): lines of a LATER launch's weight matrix pulled towards L2 / Infinity Cache; the 4 bytes
     // per lane land in the ring buffer the last K step used (free from here on; the output staging below stays under +18 KB)
     if (p.pf_lines) {
         const unsigned total_waves = gridDim.x * 4, gw = blockIdx.x * 4 + wave, n_instr = (p.pf_lines + 63) >> 6;
-        char* dump = smem + (buf == 0 ? XQ_S - 1 : buf - 1) * XQ_STAGE + 20480 + wave * 256;
+        char* dump = smem + kv2 * XQ_STAGE + 20480 + wave * 256;
         for (unsigned i = gw; i < n_instr; i += total_waves) {
             unsigned line = i * 64 + lane;
             line = line < p.pf_lines ? line : p.pf_lines - 1;
@@ -205,7 +214,7 @@ __global__ __launch_bounds__(256, 2) void xattn_q_kernel(const XattnArgs p) {
         }
     }
 
-    // ---- attention over the nt (1 or 2) key tiles, one 32-key half tile at a time (attention.hip's layouts: K rows read with bits
+    // ---- attention over the nt key tiles (1 or 2 for one prompt chunk), one 32-key half tile at a time (attention.hip's layouts: K rows read with bits
     // 2 / 3 of the row index swapped so that the 8 P values a lane owns per 16-key block are 8 consecutive keys = one 16-byte chunk
     // of a V^T row)
     const int krow = (l31 & 0x13) | ((l31 & 4) << 1) | ((l31 & 8) >> 1);
@@ -214,8 +223,18 @@ __global__ __launch_bounds__(256, 2) void xattn_q_kernel(const XattnArgs p) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[0][r] = o[1][r] = 0.f;
     float m_run = -INFINITY, l_run = 0.f;
+    int kvb = kv0;
     for (int t = 0; t < nt; ++t) {
-        const char* sK = smem + (t == 0 ? kv0 : kv1) * XQ_STAGE;
+        if (t >= 2) {
+            // streamed tile: every wave's share of tile t has landed, and every wave is past tile t - 1, whose predecessor's buffer
+            // takes tile t + 1
+            xq_wait_vmcnt<0>();
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            if (t + 1 < nt) stage_kv(kvb + 1 == XQ_S ? 0 : kvb + 1, t + 1);
+        }
+        const char* sK = smem + kvb * XQ_STAGE;
+        kvb = kvb + 1 == XQ_S ? 0 : kvb + 1;
         const char* sV = sK + 8192;
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
@@ -295,7 +314,7 @@ __global__ __launch_bounds__(256, 2) void xattn_q_kernel(const XattnArgs p) {
 
 bool supir_xattn_q_supported(const XattnArgs& a) {
     if (a.B <= 0 || a.H <= 0 || a.T <= 0 || a.Tk <= 0 || a.C <= 0) return false;
-    if (a.T % 128 || a.C % 64 || (a.C >> 6) < 3 || a.Tk > 128) return false;
+    if (a.T % 128 || a.C % 64 || (a.C >> 6) < 3) return false;
     if (a.ldx % 8 || a.ldk % 8 || a.ldvt % 8 || a.ldo % 8 || a.ldvt < ((a.Tk + 63) / 64) * 64) return false;
     if ((((size_t)a.X) | ((size_t)a.Wq) | ((size_t)a.K) | ((size_t)a.Vt) | ((size_t)a.O)) & 15) return false;
     if (a.ln_stats && (!a.ln_colsum || a.ln_slots < 0 || a.ln_slots > 64 || (a.ln_slots > 0 && a.ln_ld < a.ln_slots))) return false;

@@ -9,6 +9,7 @@ does: synthetic conditioning, no tokeniser vocabulary files in this image), or a
 """
 import contextlib
 import copy
+import os
 import random
 
 import torch
@@ -59,6 +60,11 @@ class SUPIRModel(nn.Module):
         self.ae_dtype = _DT[ae_dtype]
         self.model.dtype = _DT[diffusion_dtype]
         self.p_p, self.n_p = p_p, n_p
+        # long prompts (modules/conditioner.py): at most this many 75-token chunks per prompt; 1 = the reference's truncation at 77
+        # tokens.  SUPIR_PROMPT_CHUNKS sets the default for callers that cannot pass the keyword (the reference's own test.py).
+        self.prompt_chunks = int(os.environ.get("SUPIR_PROMPT_CHUNKS", "1"))
+        if self.prompt_chunks < 1:
+            raise ValueError(f"SUPIR_PROMPT_CHUNKS must be >= 1, got {self.prompt_chunks}")
         self._ae_dtype_noted = None
 
     # ------------------------------------------------------------------ first stage
@@ -115,8 +121,12 @@ class SUPIRModel(nn.Module):
     def batchify_sample(self, x, p=None, p_p="default", n_p="default", num_steps=100, restoration_scale=4.0, s_churn=0,
                         s_noise=1.003, cfg_scale=4.0, seed=-1, num_samples=1, control_scale=1, color_fix_type="None",
                         use_linear_CFG=False, use_linear_control_scale=False, cfg_scale_start=1.0,
-                        control_scale_start=0.0, cond=None, noises=None, return_intermediates=False, **kwargs):
-        """SUPIR_model.py:80-136.  `cond=(c, uc)` bypasses the text conditioner; `noises` (dict with optional
+                        control_scale_start=0.0, cond=None, noises=None, return_intermediates=False, prompt_chunks=None,
+                        **kwargs):
+        """SUPIR_model.py:80-136.  `cond=(c, uc)` bypasses the text conditioner (a `crossattn` longer than 77 tokens, e.g. the
+        [N, 154, 2048] of a two-chunk prompt, needs nothing else: every layer below takes the token count from the tensor);
+        `prompt_chunks` (None: self.prompt_chunks) lets prompts use up to that many 75-token chunks instead of being cut at 77 tokens
+        (prepare_condition); prompts are strings or token-id tensors [N, 77 n]; `noises` (dict with optional
         'posterior', 'init', 'steps') injects the RNG draws for parity runs (otherwise the sampler's churn noise comes from
         torch.randn_like on the device generator exactly like the reference)."""
         assert color_fix_type in ["Wavelet", "AdaIn", "None"]
@@ -125,7 +135,8 @@ class SUPIRModel(nn.Module):
             assert N == 1
             N = num_samples
             x = x.repeat(N, 1, 1, 1)
-            p = p * N if p is not None else None
+            if p is not None:
+                p = p.repeat(N, 1) if torch.is_tensor(p) else p * N
         p_p = self.p_p if p_p == "default" else p_p
         n_p = self.n_p if n_p == "default" else n_p
         sc = self.sampler_config
@@ -150,7 +161,7 @@ class SUPIRModel(nn.Module):
             c = [dict(cj, control=_z) for cj in cond[0]] if isinstance(cond[0], (list, tuple)) else dict(cond[0], control=_z)
             uc = dict(cond[1], control=_z)
         else:
-            c, uc = self.prepare_condition(_z, p, p_p, n_p, N)
+            c, uc = self.prepare_condition(_z, p, p_p, n_p, N, prompt_chunks=prompt_chunks)
         denoiser = lambda inp, sigma, cc, cs: self.denoiser(self.model, inp, sigma, cc, cs, **kwargs)
         if not kwargs:   # lets RestoreEDMSampler fuse the elementwise halves of a step around the network call (sampling.py)
             denoiser.fused = (self.denoiser, self.model)
@@ -184,31 +195,54 @@ class SUPIRModel(nn.Module):
             net.forward = VAEHook(net, size, is_decoder=dec, fast_decoder=fast_decoder, fast_encoder=fast_encoder, color_fix=color_fix,
                                   to_gpu=True, tile_chunk=tile_chunk if independent else None)
 
-    def prepare_condition(self, _z, p, p_p, n_p, N):
+    def prepare_condition(self, _z, p, p_p, n_p, N, prompt_chunks=None):
+        """SUPIR_model.py:152-180.  prompt_chunks (None: self.prompt_chunks, 1 unless SUPIR_PROMPT_CHUNKS says otherwise): a prompt
+        (caption + p_p) may fill up to that many 75-token chunks, each encoded as its own 77-token sequence; c and uc -- and with
+        per-tile prompts every tile's c -- come back with the same token count 77 n, n = the most any of them needs (at most
+        prompt_chunks), the shorter ones ending in empty chunks.  `p` / `n_p` may be token-id tensors ([N, 77 n] / [77 m] or [N, 77 m],
+        taken as they are: p_p is text and is not appended to ids)."""
         if self.conditioner is None:
             raise RuntimeError("no text conditioner attached (conditioner_config was None); pass cond=(c, uc) with "
                                "crossattn [N,77,2048] / vector [N,2816], or attach a conditioner object")
+        chunks = getattr(self, "prompt_chunks", 1) if prompt_chunks is None else int(prompt_chunks)
+        if chunks < 1:
+            raise ValueError(f"prompt_chunks must be >= 1, got {chunks}")
         batch = {"original_size_as_tuple": torch.tensor([1024, 1024]).repeat(N, 1).to(_z.device),
                  "crop_coords_top_left": torch.tensor([0, 0]).repeat(N, 1).to(_z.device),
                  "target_size_as_tuple": torch.tensor([1024, 1024]).repeat(N, 1).to(_z.device),
                  "aesthetic_score": torch.tensor([9.0]).repeat(N, 1).to(_z.device), "control": _z}
         batch_uc = copy.deepcopy(batch)
-        batch_uc["txt"] = [n_p for _ in p]
-        # the reference runs the conditioner under autocast(ae_dtype) (SUPIR_model.py:165,174): the text towers follow the VAE's request --
-        # bf16 by test.py's default, true fp32 for `--ae_dtype fp32`
-        if not isinstance(p[0], list):
-            batch["txt"] = ["".join([_p, p_p]) for _p in p]
-            with self._ae_scope():
-                return self.conditioner.get_unconditional_conditioning(batch, batch_uc)
-        # local (per-tile) prompts, SUPIR_model.py:168-178: one cond per tile, a single uc (the tiled samplers' `cond` list)
-        assert len(p) == 1, "Support bs=1 only for local prompt conditioning."
-        c, uc = [], None
-        for i, p_tile in enumerate(p[0]):
-            batch["txt"] = ["".join([p_tile, p_p])]
-            with self._ae_scope():
-                if i == 0:
-                    _c, uc = self.conditioner.get_unconditional_conditioning(batch, batch_uc)
-                else:
-                    _c, _ = self.conditioner.get_unconditional_conditioning(batch, None)
-            c.append(_c)
-        return c, uc
+        batch_uc["txt"] = (n_p if n_p.dim() == 2 else n_p[None].repeat(len(p), 1)) if torch.is_tensor(n_p) else [n_p for _ in p]
+        cond = self.conditioner
+        chunked = hasattr(cond, "prompt_chunks")
+        if not chunked and chunks != 1:
+            raise RuntimeError(f"prompt_chunks={chunks}: the attached conditioner ({type(cond).__name__}) does not chunk prompts")
+        saved = cond.prompt_chunks if chunked else None
+        if chunked:
+            cond.prompt_chunks = chunks
+        try:
+            # the reference runs the conditioner under autocast(ae_dtype) (SUPIR_model.py:165,174): the text towers follow the VAE's
+            # request -- bf16 by test.py's default, true fp32 for `--ae_dtype fp32`
+            if torch.is_tensor(p) or not isinstance(p[0], list):
+                batch["txt"] = p if torch.is_tensor(p) else ["".join([_p, p_p]) for _p in p]
+                with self._ae_scope():
+                    return cond.get_unconditional_conditioning(batch, batch_uc)
+            # local (per-tile) prompts, SUPIR_model.py:168-178: one cond per tile, a single uc (the tiled samplers' `cond` list)
+            assert len(p) == 1, "Support bs=1 only for local prompt conditioning."
+            tiles = [dict(batch, txt=p_tile[None] if torch.is_tensor(p_tile) else ["".join([p_tile, p_p])]) for p_tile in p[0]]
+            # the context bank of the tiled samplers holds one shape: every tile and the uc share one chunk count
+            pad = {"pad_to": cond.chunks_for(batch_uc, *tiles)} if chunked and hasattr(cond, "chunks_for") else {}
+            if pad and pad["pad_to"] == 1:
+                pad = {}
+            c, uc = [], None
+            for i, tile in enumerate(tiles):
+                with self._ae_scope():
+                    if i == 0:
+                        _c, uc = cond.get_unconditional_conditioning(tile, batch_uc, **pad)
+                    else:
+                        _c, _ = cond.get_unconditional_conditioning(tile, None, **pad)
+                c.append(_c)
+            return c, uc
+        finally:
+            if chunked:
+                cond.prompt_chunks = saved

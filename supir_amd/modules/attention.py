@@ -240,7 +240,7 @@ class BasicTransformerBlock(nn.Module):
             return ops.xattn_q(x, w, b, k, vt2, B, H, T, Tk, ln=st2, colsum=cs, ln_eps=e2)
 
         if ops.xattn_q_supported(B, T, C, H, Tk):
-            # to_q + the attention over the (<= 128) text keys as ONE launch where that is faster (timed once, outside graph capture)
+            # to_q + the attention over the text keys (77 per prompt chunk) as ONE launch where that is faster (timed once, outside graph capture)
             which = ops.choose(("xattn", B, T, C, H, Tk) + ops._k(x.dtype), (xattn_separate, xattn_fused), prefer=1)
             a = xattn_fused() if which == 1 else xattn_separate()
         else:

@@ -2,7 +2,7 @@
 surface as sgm/modules/encoders/modules.py (GeneralConditionerWithControl :193-243, FrozenCLIPEmbedder :445-510,
 FrozenOpenCLIPEmbedder2 :513-609, ConcatTimestepEmbedderND :1027-1043), for the embedder set options/SUPIR_v0.yaml:66-106 uses.
 
-Both text towers are pre-LN transformers over 77 tokens with head dim 64 (CLIP-L: 768 wide, 12 heads, QuickGELU, 11 of its 12 layers
+Both text towers are pre-LN transformers over 77 tokens (a long prompt is n chunks of 77, each a sequence of its own: _tokenize) with head dim 64 (CLIP-L: 768 wide, 12 heads, QuickGELU, 11 of its 12 layers
 are needed for hidden_states[11]; OpenCLIP bigG: 1280 wide, 20 heads, erf GELU, 32 layers): LayerNorm kernel, bias GEMMs with the
 activation in the epilogue, V^T projection, `supir_flash_attn_d64_ex` with the causal flag.  Runs once per image (M = 77 N rows):
 latency-trivial next to the 50 network steps, built so that `prepare_condition` never leaves the GPU.
@@ -24,18 +24,78 @@ from .base import cdt, Linear, Norm, Prep
 MAX_LENGTH = 77
 
 
-def _tokenize(texts, pad_zero):
+CHUNK_TEXT = MAX_LENGTH - 2     # ids of the prompt itself in one chunk: [BOS] + 75 + [EOS]
+
+
+def _tokenizer():
     path = os.environ.get("SUPIR_CLIP_TOKENIZER")
     if not path:
         raise RuntimeError("tokenising prompts needs the CLIP BPE vocabulary (vocab.json / merges.txt): set SUPIR_CLIP_TOKENIZER to "
                            "a directory holding them, or pass token id tensors instead of strings")
     from transformers import CLIPTokenizer
-    tok = CLIPTokenizer.from_pretrained(path)
-    ids = tok(list(texts), truncation=True, max_length=MAX_LENGTH, padding="max_length", return_tensors="pt")["input_ids"]
-    if pad_zero:   # open_clip.tokenize: [sot] tokens [eot] then zeros
-        eot = ids.argmax(dim=-1)
-        ids = ids * (torch.arange(MAX_LENGTH)[None] <= eot[:, None])
-    return ids
+    return CLIPTokenizer.from_pretrained(path)
+
+
+def _raw_ids(tok, texts):
+    return tok(list(texts), add_special_tokens=False, truncation=False, padding=False)["input_ids"]
+
+
+def _chunks_needed(texts):
+    """Chunks of 75 prompt ids the longest of `texts` fills (>= 1)."""
+    return max([1] + [-(-len(ids) // CHUNK_TEXT) for ids in _raw_ids(_tokenizer(), texts)])
+
+
+def _tokenize(texts, pad_zero, chunks=1):
+    """texts -> int64 [N, 77 n].  chunks == 1: the reference's tokenisation (truncated at 77).  chunks > 1: the prompt's ids in
+    pieces of 75, piece j as its own sequence [BOS] ids[75 j : 75 j + 75] [EOS] padded to 77 (pad id: EOS for CLIP-L, 0 for the
+    OpenCLIP tower, as for one chunk); n = min(chunks, what the longest text needs), ids past 75 n are dropped, a text that needs
+    fewer than n chunks ends in empty ones ([BOS] [EOS] pad ...)."""
+    tok = _tokenizer()
+    if chunks == 1:
+        ids = tok(list(texts), truncation=True, max_length=MAX_LENGTH, padding="max_length", return_tensors="pt")["input_ids"]
+        if pad_zero:   # open_clip.tokenize: [sot] tokens [eot] then zeros
+            eot = ids.argmax(dim=-1)
+            ids = ids * (torch.arange(MAX_LENGTH)[None] <= eot[:, None])
+        return ids
+    raw = _raw_ids(tok, texts)
+    n = min(int(chunks), max([1] + [-(-len(ids) // CHUNK_TEXT) for ids in raw]))
+    bos, eos = tok.bos_token_id, tok.eos_token_id
+    pad = 0 if pad_zero else tok.pad_token_id
+    rows = []
+    for ids in raw:
+        row = []
+        for j in range(n):
+            piece = [bos] + list(ids[CHUNK_TEXT * j:CHUNK_TEXT * (j + 1)]) + [eos]
+            row += piece + [pad] * (MAX_LENGTH - len(piece))
+        rows.append(row)
+    return torch.tensor(rows, dtype=torch.int64)
+
+
+def _check_width(tokens):
+    if tokens.dim() != 2 or tokens.shape[1] == 0 or tokens.shape[1] % MAX_LENGTH:
+        raise ValueError(f"token ids must be [N, 77 n] (n chunks of 77), got {tuple(tokens.shape)}")
+    return tokens.shape[1] // MAX_LENGTH
+
+
+def _pad_chunks(tokens, n, pad_zero):
+    """tokens [N, 77 m], m <= n -> [N, 77 n]: empty chunks appended ([BOS] [EOS] pad ...; BOS / EOS as the row's first chunk has
+    them: its first id and its largest, which is how the towers themselves find the EOS)."""
+    m = _check_width(tokens)
+    if m >= n:
+        return tokens
+    first = tokens[:, :MAX_LENGTH]
+    eos = first.max(dim=-1, keepdim=True).values
+    empty = torch.zeros_like(first) if pad_zero else eos.expand(-1, MAX_LENGTH).clone()
+    empty[:, 0:1] = first[:, 0:1]
+    empty[:, 1:2] = eos
+    return torch.cat([tokens] + [empty] * (n - m), dim=1)
+
+
+def _text_tokens(text, pad_zero, chunks, pad_to):
+    """What a text tower's forward encodes: id tensors as they are, strings through _tokenize with the chunk cap; then at least
+    `pad_to` chunks (GeneralConditioner: c and uc of one call share their token count)."""
+    tokens = text if torch.is_tensor(text) else _tokenize(text, pad_zero=pad_zero, chunks=chunks)
+    return tokens if pad_to is None else _pad_chunks(tokens, pad_to, pad_zero)
 
 
 class _Block(nn.Module):
@@ -148,7 +208,11 @@ class FrozenCLIPEmbedder(AbstractEmbModel):
         self.device, self.max_length, self.layer, self.layer_idx = device, max_length, layer, layer_idx
 
     def encode_tokens(self, tokens):
-        """tokens int64 [N, 77] -> hidden_states[layer_idx] fp32 [N, 77, 768]."""
+        """tokens int64 [N, 77 n] -> hidden_states[layer_idx] fp32 [N, 77 n, 768]: each of the n chunks is encoded as a sequence of
+        its own (positions 0..76, its own causal attention) and the hidden states are joined along the token axis."""
+        n = _check_width(tokens)
+        if n > 1:
+            return self.encode_tokens(tokens.reshape(-1, MAX_LENGTH)).reshape(tokens.shape[0], n * MAX_LENGTH, -1)
         tm = self.transformer.text_model
         dev = tm.embeddings.token_embedding.weight.device
         tokens = tokens.to(dev)
@@ -163,9 +227,8 @@ class FrozenCLIPEmbedder(AbstractEmbModel):
         return x.float()
 
     @torch.no_grad()
-    def forward(self, text):
-        tokens = text if torch.is_tensor(text) else _tokenize(text, pad_zero=False)
-        return self.encode_tokens(tokens)
+    def forward(self, text, chunks=1, pad_to=None):
+        return self.encode_tokens(_text_tokens(text, False, chunks, pad_to))
 
     def encode(self, text):
         return self(text)
@@ -241,7 +304,13 @@ class FrozenOpenCLIPEmbedder2(AbstractEmbModel):
         self.device, self.max_length, self.layer, self.return_pooled, self.legacy = device, max_length, layer, True, legacy
 
     def encode_tokens(self, tokens):
-        """tokens int64 [N, 77] -> (penultimate fp32 [N, 77, D], pooled fp32 [N, out_dim])."""
+        """tokens int64 [N, 77 n] -> (penultimate fp32 [N, 77 n, D], pooled fp32 [N, out_dim]).  Each chunk is a sequence of its own;
+        the pooled output is chunk 0's (the SDXL convention of the front ends that chunk prompts: `vector` keeps its width)."""
+        n = _check_width(tokens)
+        if n > 1:
+            N = tokens.shape[0]
+            pen, pooled = self.encode_tokens(tokens.reshape(-1, MAX_LENGTH))
+            return pen.reshape(N, n * MAX_LENGTH, -1), pooled.reshape(N, n, -1)[:, 0].contiguous()
         m = self.model
         dev = m.positional_embedding.device
         tokens = tokens.to(dev)
@@ -262,9 +331,8 @@ class FrozenOpenCLIPEmbedder2(AbstractEmbModel):
         return pen.float(), pooled
 
     @torch.no_grad()
-    def forward(self, text):
-        tokens = text if torch.is_tensor(text) else _tokenize(text, pad_zero=True)
-        return self.encode_tokens(tokens)
+    def forward(self, text, chunks=1, pad_to=None):
+        return self.encode_tokens(_text_tokens(text, True, chunks, pad_to))
 
     def encode(self, text):
         return self(text)
@@ -315,21 +383,47 @@ class GeneralConditioner(nn.Module):
             e.legacy_ucg_val = cfg.get("legacy_ucg_value", None)
             embedders.append(e.eval())
         self.embedders = nn.ModuleList(embedders)
+        # long prompts: at most this many 75-token chunks per prompt, each encoded as its own 77-token sequence and joined along the
+        # token axis (crossattn [N, 77 n, 2048]); 1 = the reference's truncation at 77 tokens
+        self.prompt_chunks = 1
+
+    @staticmethod
+    def _is_text_tower(e):
+        return isinstance(e, (FrozenCLIPEmbedder, FrozenOpenCLIPEmbedder2))
+
+    def chunks_for(self, *batches):
+        """The chunk count every text input of `batches` is brought to: id tensors count as they are, strings up to prompt_chunks."""
+        n = 1
+        cap = int(self.prompt_chunks)
+        for batch in batches:
+            for e in self.embedders:
+                if batch is None or not self._is_text_tower(e):
+                    continue
+                t = batch[e.input_key]
+                if torch.is_tensor(t):
+                    n = max(n, _check_width(t))
+                elif cap > 1:
+                    n = max(n, min(cap, _chunks_needed(t)))
+        return n
 
     def _key_of(self, embedder, emb):
         return self.OUTPUT_DIM2KEYS[emb.dim()]
 
     @torch.no_grad()
-    def forward(self, batch, force_zero_embeddings=None):
+    def forward(self, batch, force_zero_embeddings=None, pad_to=None):
         output = {}
         force_zero_embeddings = force_zero_embeddings or []
+        cap = int(self.prompt_chunks)
         for e in self.embedders:
             if e.ucg_rate > 0.0:
                 # training-time conditioning dropout (modules.py:217-228; legacy_ucg_value only acts together with ucg_rate > 0,
                 # :121-134): never active on the inference path, where get_unconditional_conditioning sets every rate to 0
                 # (:177-186); a direct forward() with a live rate is refused rather than silently ignored
                 raise NotImplementedError("ucg_rate > 0 is a training-time option of the reference (conditioning dropout)")
-            out = e(batch[e.input_key])
+            if self._is_text_tower(e) and (cap > 1 or pad_to is not None):
+                out = e(batch[e.input_key], chunks=cap, pad_to=pad_to)
+            else:
+                out = e(batch[e.input_key])
             for emb in (out if isinstance(out, (list, tuple)) else [out]):
                 key = self._key_of(e, emb)
                 if e.input_key in force_zero_embeddings:
@@ -337,15 +431,19 @@ class GeneralConditioner(nn.Module):
                 output[key] = torch.cat((output[key], emb), self.KEY2CATDIM[key]) if key in output else emb
         return output
 
-    def get_unconditional_conditioning(self, batch_c, batch_uc=None, force_uc_zero_embeddings=None):
+    def get_unconditional_conditioning(self, batch_c, batch_uc=None, force_uc_zero_embeddings=None, pad_to=None):
         """modules.py:177-191: every embedder's ucg_rate is zeroed for the two encodes and restored afterwards, so a config that
-        carries training-time rates still serves inference."""
+        carries training-time rates still serves inference.  c and uc come back with the same token count (CFG stacks them along the
+        batch axis): the chunk count is resolved once over both, and the shorter side ends in empty chunks.  pad_to: a chunk count
+        resolved by the caller over MORE than this pair (the per-tile prompts of one image, SUPIRModel.prepare_condition)."""
+        n = max(self.chunks_for(batch_c, batch_uc), pad_to or 1)
+        pad = {} if n == 1 else {"pad_to": n}
         rates = [e.ucg_rate for e in self.embedders]
         for e in self.embedders:
             e.ucg_rate = 0.0
         try:
-            c = self(batch_c)
-            uc = self(batch_c if batch_uc is None else batch_uc, force_uc_zero_embeddings or [])
+            c = self(batch_c, **pad)
+            uc = self(batch_c if batch_uc is None else batch_uc, force_uc_zero_embeddings or [], **pad)
         finally:
             for e, r in zip(self.embedders, rates):
                 e.ucg_rate = r
@@ -358,7 +456,7 @@ class GeneralConditionerWithControl(GeneralConditioner):
     def _key_of(self, embedder, emb):
         return "control_vector" if "control_vector" in embedder.input_key else self.OUTPUT_DIM2KEYS[emb.dim()]
 
-    def forward(self, batch, force_zero_embeddings=None):
-        output = super().forward(batch, force_zero_embeddings)
+    def forward(self, batch, force_zero_embeddings=None, pad_to=None):
+        output = super().forward(batch, force_zero_embeddings, pad_to)
         output["control"] = batch["control"]
         return output

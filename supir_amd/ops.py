@@ -1218,13 +1218,14 @@ USE_XATTN = _os.environ.get("SUPIR_FUSED_XATTN", "1") != "0"
 
 
 def xattn_q_supported(B, T, C, H, Tk):
-    """Shape predicate of supir_xattn_q_d64 (csrc/xattn.hip): whole 128-token row blocks, K steps of 64 channels, <= 2 key tiles."""
-    return USE_XATTN and T % 128 == 0 and C % 64 == 0 and C >= 192 and 0 < Tk <= 128 and H > 0
+    """Shape predicate of supir_xattn_q_d64 (csrc/xattn.hip): whole 128-token row blocks, K steps of 64 channels, any number of
+    keys (one 77-token prompt chunk is two key tiles; a chunked long prompt streams 154 / 231 / ... keys through the same ring)."""
+    return USE_XATTN and T % 128 == 0 and C % 64 == 0 and C >= 192 and Tk > 0 and H > 0
 
 
 def xattn_q(x, wq, bias, k, vt, B, H, T, Tk, *, ln=None, colsum=None, ln_eps=1e-5, out=None):
-    """to_q projection (optionally with the LayerNorm fold of gemm_ln) + attention over the Tk <= 128 cached text keys, one launch:
-    x [B,T,C] tokens, wq [H*64,C], k [B,Tk,H*64], vt [B,H*64,Tpad] -> [B,T,H*64].  Callers check xattn_q_supported first."""
+    """to_q projection (optionally with the LayerNorm fold of gemm_ln) + attention over the Tk cached text keys (any Tk > 0), one launch:
+    x [B,T,C] tokens, wq [H*64,C], k [B,Tk,H*64], vt [B,H*64,Tpad >= roundup(Tk, 64)] -> [B,T,H*64].  Callers check xattn_q_supported first."""
     DT = x.dtype
     lib = _lib.load(DT)
     _check_dev(x, wq, k, vt)
