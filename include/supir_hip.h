@@ -174,6 +174,25 @@ int supir_conv3x3_bf16_ex(const void* X, const void* W, void* Y, int B, int H, i
                           const void* rowbias, int ld_rowbias, const void* residual, int ldr, int act, int out_mode,
                           float alpha, int tile, const supir_launch_hints* hints, void* stream);
 
+/* The gamma|beta convolution of a ZeroSFT adapter fused with the adapter's GroupNorm + modulation (SUPIR/modules/SUPIR_v0.py:62-113):
+ *     out = GN(cat[x1, x2]) * (zero_mul(A) + 1) + zero_add(A),   then   out * cs + cat[x1raw, x2raw] * (1 - cs)   when cs != 1
+ * in ONE launch: what supir_conv3x3_bf16_ex (128 -> 2 C) followed by supir_groupnorm_nhwc_parts (mod_g / mod_b) compute, without the
+ * [tokens][2 C] map between them.  Same arithmetic: the two modulation values are rounded to the 16-bit element type before use.
+ *   A:[B][H][Wd][lda] = SiLU(mlp_shared(c)); Wgb:[2 C][3][3][Cin], bias_gb:[2 C] -- zero_mul / zero_add INTERLEAVED in blocks of 16
+ *   output channels (rows 32 i + r = zero_mul row 16 i + r, rows 32 i + 16 + r = zero_add row 16 i + r, r < 16); out:[B][H][Wd][ldo];
+ *   x1 / x2 / x1raw / x2raw / C1 / ld1 / ld2 / gamma / beta / eps / part1 / nchunk1 / part2 / nchunk2 as in supir_groupnorm_nhwc_parts;
+ *   control_scale_cell != NULL: cs is loaded from that 4-byte device cell when the kernel runs (as supir_groupnorm_nhwc_parts_dyn; the
+ *   caller then passes the raw operands whatever the cell will hold), else cs = control_scale.
+ * hints->gn_partials_out: [B][H Wd / BM][C / 10][2] (sum, sum of squares) of the values stored, as the plain epilogues write them.
+ * tile: 33 (128 x 160, BM = 128) or 34 (256 x 160, BM = 256), in their one-wave-column forms.  Conditions, else SUPIR_ERR_SHAPE before
+ * any HIP call: C % 320 == 0, C1 % 80 == 0, H Wd % BM == 0, Cin % 64 (tile 33: 128) == 0, lda / ldo % 8 == 0, ld1 / ld2 % 4 == 0,
+ * 8-byte aligned x operands, 16-byte aligned out, part1 (and part2 when C1 < C) given. */
+int supir_conv3x3_zerosft(const void* A, const void* Wgb, const float* bias_gb, void* out, int B, int H, int Wd, int Cin, int lda, int C,
+                          int ldo, const void* x1, const void* x2, const void* x1raw, const void* x2raw, int C1, int ld1, int ld2,
+                          const float* gamma, const float* beta, float eps, const float* part1, int nchunk1, const float* part2,
+                          int nchunk2, float control_scale, const float* control_scale_cell, int tile, const supir_launch_hints* hints,
+                          void* stream);
+
 /* softmax(Q K^T * scale) V for head dim 64.  Q:[B][Tq][ldq], K:[B][Tk][ldk] with head h at columns h*64..h*64+63;
  * Vt:[B][H*64][ldvt] is V transposed per batch (SUPIR_OUT_BF16_T output of the to_v projection), ldvt >= roundup(Tk,64),
  * padding finite; O:[B][Tq][ldo] (ldo % 8 == 0 and a 16-byte aligned O take the row-contiguous 16-byte store path; ldo % 4 is accepted).

@@ -113,6 +113,9 @@ SIGNATURES.update({
     # Q, K, Vt, O, B, Tq, Tk, ldq, ldk, ldvt, ldo, scale, splits, workspace, workspace_bytes, stream
     "supir_flash_attn_d512_split": [P, P, P, P, I, I, I, I, I, I, I, F, I, P, c_size_t, P],
     "supir_groupnorm_grouped": [P, I, I, I, I, F, I, P],
+    # A, Wgb, bias_gb, out, B, H, Wd, Cin, lda, C, ldo, x1, x2, x1raw, x2raw, C1, ld1, ld2, gamma, beta, eps, part1, nchunk1, part2, nchunk2,
+    # control_scale, control_scale_cell, tile, hints, stream
+    "supir_conv3x3_zerosft": [P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, I, I, I, P, P, F, P, I, P, I, F, P, I, P, P],
 })
 # dynamic control scale: the same launches with the float control_scale / alpha replaced by a pointer to a 4-byte device cell
 SIGNATURES.update({

@@ -188,6 +188,32 @@ int supir_conv3x3_bf16_ex(const void* X, const void* W, void* Y, int B, int H, i
     return supir_gemm_launch(a, true, (hipStream_t)stream, tile);
 }
 
+// The gamma|beta convolution of a ZeroSFT adapter fused with its GroupNorm + modulation (include/supir_hip.h; SUPIR/modules/SUPIR_v0.py:62-113):
+// validation + packing; the shape conditions are supir_gemm16_zsft_supported's.
+int supir_conv3x3_zerosft(const void* A, const void* Wgb, const float* bias_gb, void* out, int B, int H, int Wd, int Cin, int lda, int C,
+                          int ldo, const void* x1, const void* x2, const void* x1raw, const void* x2raw, int C1, int ld1, int ld2,
+                          const float* gamma, const float* beta, float eps, const float* part1, int nchunk1, const float* part2,
+                          int nchunk2, float control_scale, const float* control_scale_cell, int tile, const supir_launch_hints* hints,
+                          void* stream) {
+    if (!A || !Wgb || !bias_gb || !out || !x1 || !gamma || !beta || !part1) return SUPIR_ERR_ARG;
+    if (B <= 0 || H <= 0 || Wd <= 0 || Cin <= 0 || C <= 0) return SUPIR_ERR_ARG;
+    if (tile != 33 && tile != 34) return SUPIR_ERR_SHAPE;
+    if ((long)B * H * Wd >= (1L << 31) || C >= (1 << 29)) return SUPIR_ERR_SHAPE;
+    GemmArgs a{};
+    a.A = (const bf16_t*)A; a.Wt = (const bf16_t*)Wgb; a.C = out; a.bias = bias_gb;
+    a.M = B * H * Wd; a.N = 2 * C; a.K = 9 * Cin; a.lda = lda; a.ldc = ldo;
+    a.rows_per_batch = H * Wd;
+    a.H = H; a.W = Wd; a.Cin = Cin; a.OH = H; a.OW = Wd; a.stride = 1; a.pad_t = 1; a.pad_l = 1;
+    a.alpha = 1.0f;
+    if (const int rc = apply_hints(a, hints)) return rc;
+    ZsftArgs z{};
+    z.x1 = (const bf16_t*)x1; z.x2 = (const bf16_t*)x2; z.x1raw = (const bf16_t*)x1raw; z.x2raw = (const bf16_t*)x2raw;
+    z.gamma = gamma; z.beta = beta; z.part_u1 = part1; z.part_u2 = part2; z.cscale_cell = control_scale_cell;
+    z.C = C; z.C1 = C1; z.ld1 = ld1; z.ld2 = ld2; z.nch1 = nchunk1; z.nch2 = nchunk2;
+    z.eps = eps; z.cscale = control_scale;
+    return supir_gemm16_zsft_launch(a, z, (hipStream_t)stream, tile);
+}
+
 int supir_conv3x3_bf16(const void* X, const void* W, void* Y, int B, int H, int Wd, int Cin, int ldx, int Cout,
                        int ldy, int OH, int OW, int stride, int pad_t, int pad_l, int upsample, const float* bias,
                        const void* rowbias, int ld_rowbias, const void* residual, int ldr, int act, int out_mode,

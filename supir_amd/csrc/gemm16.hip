@@ -128,6 +128,66 @@ __global__ __launch_bounds__(64 * WM * WN * KS, (WM * WN * KS == 8 ? 2 : 1)) voi
 #include "gemm16_body.inc"
 }
 
+// The stride-1 3 x 3 convolution tile with the ZeroSFT epilogue (SUPIR/modules/SUPIR_v0.py:62-113): the convolution is zero_mul | zero_add
+// (W rows interleaved [16 gamma | 16 beta]) and the epilogue applies GroupNorm(cat[x1, x2]) * (gamma + 1) + beta with the control-scale
+// lerp instead of storing the two maps -- what conv3x3 + gn_apply_kernel<1, true, false> compute in two launches and a round trip of
+// a [tokens][2 C] map through memory.  Same loader, ring and main loop as gemm16_kernel's convolution form; its own instantiations
+// (one wave column: the (gamma, beta) fragment pairs lie in one lane), so no other launch changes.
+template <int BM, int BN, int WM, int WN, int KS, int S, int HW_ = 0>
+__global__ __launch_bounds__(64 * WM * WN * KS, 2) void gemm16_zsft_kernel(const GemmArgsN<1> pp, const ZsftArgs zs) {
+    constexpr bool TRANS = false, CONV = true, MIXED = false;
+    constexpr int NP = 1;
+#define SUPIR_G16_ZSFT
+#include "gemm16_body.inc"
+#undef SUPIR_G16_ZSFT
+}
+
+template <int BM, int BN, int WM, int WN, int KS, int S>
+static int launch_gemm16_zsft(const GemmArgs& a_in, const ZsftArgs& zs, hipStream_t st) {
+    GemmArgsN<1> pp;
+    pp.p[0] = a_in;
+    GemmArgs& a = pp.p[0];
+    a.korder = 0;
+    const int tiles = (a.M / BM) * (a.N / BN);
+    supir_choose_xcd_grid(a, a.M / BM, a.N / BN, 2.0 * (double)a.M * a.Cin, 2.0 * (double)a.N * a.K, 9, 1, 8);
+    constexpr int smem = KS * S * (BM + BN) * 128 + 256 + 1024;   // the rings, the prefetch scratch row, sa | sb of the tile's 80 channels
+    static_assert(smem <= 163840, "LDS");
+    auto kern = gemm16_zsft_kernel<BM, BN, WM, WN, KS, S>;
+    static bool attr_set = false;
+    if (!attr_set) {
+        if (supir_note_hip_status(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem)) != SUPIR_OK) return SUPIR_ERR_HIP;
+        attr_set = true;
+    }
+    SUPIR_LAUNCH(kern, dim3(tiles), dim3(64 * WM * WN * KS), smem, st, pp, zs);
+    return SUPIR_LAUNCH_STATUS();
+}
+
+// tiles 33 (128 x 160, two K groups of 4 x 1 waves) and 34 (256 x 160, 8 x 1 waves).  a: the convolution 128 -> 2 C with the
+// interleaved weights (a.N = 2 C; a.C / a.ldc = the [tokens][C] output); z: the GroupNorm / modulation operands
+bool supir_gemm16_zsft_supported(const GemmArgs& a, const ZsftArgs& z, int tile) {
+    if (tile != 33 && tile != 34) return false;
+    const int bm = tile == 34 ? 256 : 128, ks = tile == 34 ? 1 : 2, s = tile == 34 ? 3 : 2;
+    // the convolution: exact tiles, stride 1, pad 1, no upsampling, no other epilogue term
+    if (a.M % bm || a.N % 160 || a.K % (64 * ks) || a.lda % 8 || (a.K >> 6) / ks < s - 1 || a.Cin % (64 * ks) || a.K != 9 * a.Cin) return false;
+    if (a.stride != 1 || a.up || a.pad_t != 1 || a.pad_l != 1 || a.OH != a.H || a.OW != a.W) return false;
+    if (a.out_mode != 0 || a.act != 0 || a.res || a.rowbias || a.ln_stats || a.rowstats_out || a.alpha != 1.0f || !a.bias) return false;
+    if (a.ldc % 8 || (((size_t)a.C) & 15)) return false;
+    // tile rows never straddle a batch element; a tile's 80 channels never straddle the two concat sources; the GroupNorm groups and both
+    // sources are whole 10-channel partial units
+    if (a.rows_per_batch != a.OH * a.OW || a.rows_per_batch % bm) return false;
+    if (z.C <= 0 || a.N != 2 * z.C || z.C % 320 || z.C1 <= 0 || z.C1 > z.C || z.C1 % 80 || (z.C1 < z.C && !z.x2)) return false;
+    if (!z.x1 || !z.gamma || !z.beta || !z.part_u1 || z.nch1 <= 0 || (z.C1 < z.C && (!z.part_u2 || z.nch2 <= 0))) return false;
+    if (z.ld1 % 4 || (z.C1 < z.C && z.ld2 % 4) || z.ld1 < z.C1 || (z.C1 < z.C && z.ld2 < z.C - z.C1)) return false;
+    if ((((size_t)z.x1) | ((size_t)z.x2) | ((size_t)z.x1raw) | ((size_t)z.x2raw)) & 7) return false;
+    return true;
+}
+
+int supir_gemm16_zsft_launch(const GemmArgs& a, const ZsftArgs& z, hipStream_t st, int tile) {
+    if (!supir_gemm16_zsft_supported(a, z, tile)) return SUPIR_ERR_SHAPE;
+    if (tile == 34) return launch_gemm16_zsft<256, 160, 8, 1, 1, 3>(a, z, st);
+    return launch_gemm16_zsft<128, 160, 4, 1, 2, 2>(a, z, st);
+}
+
 template <int BM, int BN, int WM, int WN, int KS, int S, bool TRANS, bool CONV = false, bool MIXED = false, int NP = 1, int HW_ = 0>
 static int launch_gemm16(const GemmArgs* a_in, hipStream_t st, const float* alpha_cell = nullptr) {
     GemmArgsN<NP> pp;

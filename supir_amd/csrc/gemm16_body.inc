@@ -451,6 +451,67 @@
         }
     }
 
+#ifdef SUPIR_G16_ZSFT
+    // ---- ZeroSFT epilogue (gemm16_zsft_kernel; zs = ZsftArgs): W rows interleaved [16 gamma | 16 beta], so this tile's BN columns are the
+    // modulation maps of BN / 2 = 80 output channels [zs_c0, zs_c0 + 80) of ONE batch element.  GroupNorm statistics of that batch element
+    // from the producers' partials, as gn_apply_body.inc reads them (10-channel units of the two concat sources, fp64 sums -- exact for
+    // these counts, so the split over lanes does not show -- the same var >= 0 clamp and 1 / sqrt(var + eps)), reduced HERE, behind the
+    // first stages' loads: wave w takes the w-th group the tile's channels touch (<= 8: groups are >= 10 channels wide), 32 lanes per
+    // statistic over (tile row, unit), a fixed xor tree across them; then sa = rstd * gamma, sb = beta - mean * sa of the group's channels
+    // inside the tile go to LDS beyond the rings.  Every load is consumed before the loop: its counted waits see only stage loads.
+    static_assert(CONV && !HALO && !TRANS && !MIXED && NP == 1 && WN == 1 && BN == 160 && (NI & 1) == 0 && S != 8, "ZeroSFT epilogue: 160-column tiles, one wave column");
+    constexpr int ZS_CH = BN / 2;
+    constexpr int OFF_ZS = KS * RING + 256;        // [ZS_CH] sa | [ZS_CH] sb, behind the rings and the prefetch scratch row
+    const int zs_c0 = n0 >> 1;
+    const float zs_cs = zs.cscale_cell ? *zs.cscale_cell : zs.cscale;
+    {
+        const int zb = m0 / p.rows_per_batch;
+        const int cpg = zs.C >> 5, upg = cpg / 10, U1 = zs.C1 / 10, U2 = (zs.C - zs.C1) / 10;
+        const int g = zs_c0 / cpg + bwave;
+        if (g * cpg < zs_c0 + ZS_CH) {               // wave-uniform
+            const int st = lane & 1, l = lane >> 1;
+            // the group's units [g upg, (g + 1) upg) of the concatenation: [a1, a1 + w1) of source 1, [a2, a2 + w2) of source 2
+            const int u_lo = g * upg, u_hi = u_lo + upg;
+            const int a1 = u_lo < U1 ? u_lo : U1, w1 = (u_hi < U1 ? u_hi : U1) - a1;
+            const int a2 = (u_lo > U1 ? u_lo : U1) - U1, w2 = upg - w1;
+            const int tot1 = w1 * zs.nch1, tot = tot1 + w2 * zs.nch2;
+            double a = 0.0;
+            for (int i0 = l; i0 < tot; i0 += 128) {
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {        // four independent loads in flight; beyond the end: a repeat of element 0, weight 0
+                    const int idx = i0 + 32 * e;
+                    const bool ok = idx < tot;
+                    const int ii = ok ? idx : 0;
+                    const bool first = ii < tot1;
+                    const int j = first ? ii : ii - tot1, w = first ? w1 : w2;
+                    const int k = j / w, u = (first ? a1 : a2) + (j - k * w);
+                    const float* src = first ? zs.part_u1 : zs.part_u2;
+                    const int nch = first ? zs.nch1 : zs.nch2, Un = first ? U1 : U2;
+                    const float f = src[(((size_t)zb * nch + k) * Un + u) * 2 + st];
+                    v[e] = ok ? f : 0.f;
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) a += (double)v[e];
+            }
+#pragma unroll
+            for (int o = 2; o < 64; o <<= 1) a += __shfl_xor(a, o, 64);
+            const double sum = __shfl(a, 0, 64), sq = __shfl(a, 1, 64);
+            const double n = (double)p.rows_per_batch * (double)cpg;
+            const double mean = sum / n;
+            double var = sq / n - mean * mean;
+            var = var > 0.0 ? var : 0.0;
+            const float mean_f = (float)mean, rstd_f = (float)(1.0 / sqrt(var + (double)zs.eps));
+            const int c_lo = g * cpg > zs_c0 ? g * cpg : zs_c0, c_hi = (g + 1) * cpg < zs_c0 + ZS_CH ? (g + 1) * cpg : zs_c0 + ZS_CH;
+            float* s_sa = (float*)(smem + OFF_ZS);
+            for (int c = c_lo + lane; c < c_hi; c += 64) {
+                const float sa = rstd_f * zs.gamma[c];
+                s_sa[c - zs_c0] = sa;
+                s_sa[ZS_CH + c - zs_c0] = zs.beta[c] - mean_f * sa;
+            }
+        }
+    }
+#endif
     // one K step.  STAGE: also issue the global->LDS loads of tile kt + S - 1 (into the buffer step kt - 1 just finished reading),
     // spread over the two 32-wide K slices; INFLIGHT: younger stages that may stay outstanding across this step's barrier
     int buf = 0, sbuf = S - 1;   // ring positions of the tile being read / being staged (kept modulo S without a division)
@@ -808,6 +869,114 @@
                 }
             }
         };
+#ifdef SUPIR_G16_ZSFT
+        {
+            // ZeroSFT: fragment pair (2 jp, 2 jp + 1) = (gamma, beta) map of 16 output channels, both rounded to the 16-bit element type as
+            // the two-launch path stores them; out = (x sa + sb) (gamma + 1) + beta, lerp against the raw operand when the control scale is
+            // not 1 -- the expressions of gn_apply_body.inc.  x comes from the concat source this tile's channels lie in (wave-uniform:
+            // C1 % 80 == 0).  The 16 x 80 block is staged and stored like the GEGLU block; its column sums are the GroupNorm partials
+            // of the OUTPUT for the consumer (10-channel units, the slot layout of the plain epilogue with N / 2 channels)
+            const float* s_sa = (const float*)(smem + OFF_ZS);
+            const float* s_sb = s_sa + ZS_CH;
+            const bool zs_first = zs_c0 < zs.C1;
+            const bf16_t* xs = zs_first ? zs.x1 : zs.x2;
+            const bf16_t* xr = zs_first ? (zs.x1raw ? zs.x1raw : zs.x1) : (zs.x2raw ? zs.x2raw : zs.x2);
+            const int zs_ld = zs_first ? zs.ld1 : zs.ld2, zs_cx = zs_first ? zs_c0 : zs_c0 - zs.C1;
+            const bool lerp = zs_cs != 1.0f;
+            auto run = [&](auto kg_c) {
+                constexpr int KG = decltype(kg_c)::value;
+                constexpr int GP = (ZS_CH + 63) / 64;
+                float gsum[GP], gsq[GP];
+#pragma unroll
+                for (int g = 0; g < GP; ++g) gsum[g] = gsq[g] = 0.f;
+#pragma unroll
+                for (int h = 0; h < MIH; ++h) {
+                    const int mrow = wm * WTM + (KG * MIH + h) * 16;
+                    const size_t xo = (size_t)(m0 + mrow + l15) * zs_ld + zs_cx + 4 * quad;
+                    u32x2 xv[NI / 2], rv[NI / 2];
+#pragma unroll
+                    for (int jp = 0; jp < NI / 2; ++jp) xv[jp] = rv[jp] = *(const u32x2*)(xs + xo + jp * 16);
+                    if (lerp) {
+#pragma unroll
+                        for (int jp = 0; jp < NI / 2; ++jp) rv[jp] = *(const u32x2*)(xr + xo + jp * 16);
+                    }
+#pragma unroll
+                    for (int jp = 0; jp < NI / 2; ++jp) {
+                        const int nl = jp * 32 + 4 * quad, cl = jp * 16 + 4 * quad;
+                        const f32x4 bg = *(const f32x4*)(s_bias + nl), bb = *(const f32x4*)(s_bias + nl + 16);
+                        const f32x4 sa = *(const f32x4*)(s_sa + cl), sb = *(const f32x4*)(s_sb + cl);
+                        const f32x4_t ag = acc[KG * MIH + h][2 * jp], ab = acc[KG * MIH + h][2 * jp + 1];
+                        const u32x2 gq = {f2bf_pk(ag[0] + bg[0], ag[1] + bg[1]), f2bf_pk(ag[2] + bg[2], ag[3] + bg[3])};
+                        const u32x2 bq = {f2bf_pk(ab[0] + bb[0], ab[1] + bb[1]), f2bf_pk(ab[2] + bb[2], ab[3] + bb[3])};
+                        float r[4];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float x = (e & 1) ? bfhi2f(xv[jp][e >> 1]) : bflo2f(xv[jp][e >> 1]);
+                            const float gm = (e & 1) ? bfhi2f(gq[e >> 1]) : bflo2f(gq[e >> 1]);
+                            const float bt = (e & 1) ? bfhi2f(bq[e >> 1]) : bflo2f(bq[e >> 1]);
+                            float y = x * sa[e] + sb[e];
+                            y = y * (gm + 1.0f) + bt;
+                            if (lerp) y = y * zs_cs + ((e & 1) ? bfhi2f(rv[jp][e >> 1]) : bflo2f(rv[jp][e >> 1])) * (1.0f - zs_cs);
+                            r[e] = y;
+                        }
+                        const u32x2 o = {f2bf_pk(r[0], r[1]), f2bf_pk(r[2], r[3])};
+                        *(u32x2*)(c_stage + l15 * C_RS + cl * 2) = o;
+                    }
+                    flush_block(m0 + mrow, zs_c0, std::integral_constant<int, ZS_CH>{});
+                    if (p.gn_part_out) {
+#pragma unroll
+                        for (int g = 0; g < GP; ++g) {
+                            const int col = g * 64 + lane;
+                            if (ZS_CH % 64 == 0 || col < ZS_CH) {
+                                float cs_ = 0.f, cq_ = 0.f;
+#pragma unroll
+                                for (int row = 0; row < 16; ++row) {
+                                    const float f = bf2f(*(const u16*)(c_stage + row * C_RS + col * 2));
+                                    cs_ += f;
+                                    cq_ += f * f;
+                                }
+                                gsum[g] += cs_;
+                                gsq[g] += cq_;
+                            }
+                        }
+                    }
+                }
+                if (p.gn_part_out) {
+                    float* red = (float*)(smem + OFF_GN) + (size_t)bwave * WTN * 2;
+#pragma unroll
+                    for (int g = 0; g < GP; ++g) {
+                        const int col = g * 64 + lane;
+                        if (ZS_CH % 64 == 0 || col < ZS_CH) {
+                            red[col * 2] = gsum[g];
+                            red[col * 2 + 1] = gsq[g];
+                        }
+                    }
+                }
+            };
+            if (kg == 0) run(K0_{});
+            else if constexpr (KS == 2) run(K1_{});
+            if (p.gn_part_out) {   // one (sum, sum of squares) per 10-channel unit of the tile: every wave (all wave rows, both K groups), fixed order
+                __syncthreads();
+                if ((int)threadIdx.x < ZS_CH / 10) {
+                    const float* red = (const float*)(smem + OFF_GN);
+                    float sm = 0.f, sq = 0.f;
+                    for (int c = (int)threadIdx.x * 10; c < (int)threadIdx.x * 10 + 10; ++c) {
+#pragma unroll
+                        for (int bw = 0; bw < NWT; ++bw) {
+                            sm += red[((size_t)bw * WTN + c) * 2];
+                            sq += red[((size_t)bw * WTN + c) * 2 + 1];
+                        }
+                    }
+                    const int b = m0 / p.rows_per_batch, chunk = (m0 - b * p.rows_per_batch) / BM, nchunk = p.rows_per_batch / BM;
+                    float* dst = p.gn_part_out + (((size_t)b * nchunk + chunk) * (p.N / 20) + zs_c0 / 10 + threadIdx.x) * 2;
+                    dst[0] = sm;
+                    dst[1] = sq;
+                }
+            }
+            prefetch_next();
+            return;
+        }
+#endif
         if (p.act == 2) {
             // GEGLU: W rows interleaved [16 value | 16 gate]: fragment pair (2 jp, 2 jp + 1) = (value, gate) of 16 output columns
             if constexpr ((NI & 1) == 0) {

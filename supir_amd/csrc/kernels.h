@@ -54,6 +54,23 @@ struct GemmArgsN {
     GemmArgs p[NP];
 };
 
+// ZeroSFT epilogue of the gamma|beta convolution (supir_conv3x3_zerosft, csrc/gemm16.hip gemm16_zsft_kernel): the operands of the
+// GroupNorm + modulation the two-launch path hands to gn_apply_kernel<1, true, false> (GnArgs below, same meanings).  A kernel
+// argument of its own: GemmArgs -- the argument block of every other GEMM-family kernel -- stays what it was.
+struct ZsftArgs {
+    const bf16_t* x1;      // [B][HW][ld1], channels [0, C1) of the concatenation
+    const bf16_t* x2;      // [B][HW][ld2], channels [C1, C)  (null when C1 == C)
+    const bf16_t* x1raw;   // lerp only: raw counterpart of x1 (null -> x1 itself)
+    const bf16_t* x2raw;   // lerp only: raw counterpart of x2 (null -> x2 itself)
+    const float* gamma;    // [C] GroupNorm affine
+    const float* beta;     // [C]
+    const float* part_u1;  // producer partials of x1: [B][nch1][C1 / 10][2]
+    const float* part_u2;  //          ... of x2: [B][nch2][(C - C1) / 10][2]
+    const float* cscale_cell;  // non-null: the control scale is loaded from this 4-byte device cell when the kernel runs
+    int C, C1, ld1, ld2, nch1, nch2;
+    float eps, cscale;
+};
+
 struct AttnArgs {
     const bf16_t* Q;
     const bf16_t* K;
@@ -132,6 +149,9 @@ void supir_choose_xcd_grid(GemmArgs& a, int tiles_m, int tiles_n, double a_bytes
 bool supir_gemm16_supported(const GemmArgs& a, int tile, bool conv);
 int supir_gemm16_launch(const GemmArgs& a, hipStream_t st, int tile, bool conv, const float* alpha_cell = nullptr);
 int supir_gemm16_qkv_launch(const GemmArgs& a, hipStream_t st);
+// the gamma|beta convolution of a ZeroSFT adapter with the GroupNorm + modulation epilogue (tiles 33 / 34 in their one-wave-column forms)
+bool supir_gemm16_zsft_supported(const GemmArgs& a, const ZsftArgs& z, int tile);
+int supir_gemm16_zsft_launch(const GemmArgs& a, const ZsftArgs& z, hipStream_t st, int tile);
 // grouped forms: n (1 or 2) problems of identical shape, one launch (tiles 33 / 34 / 35 and the fused q|k|v tile)
 int supir_gemm16_launch_n(const GemmArgs* a, int n, hipStream_t st, int tile, bool conv);
 int supir_gemm16_qkv_launch_n(const GemmArgs* a, int n, hipStream_t st);

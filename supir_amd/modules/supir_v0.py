@@ -17,8 +17,11 @@ class ZeroSFT(nn.Module):
     lerp with control_scale against cat[h_ori, h].
 
     Launches: 1x1 GEMM with the skip as residual epilogue; conv3x3(Cc->128)+SiLU epilogue; ONE conv3x3(128 -> 2*C) for
-    gamma|beta (weights concatenated); GroupNorm stats; GroupNorm apply fused with the modulation, the lerp and the
-    channel concat (two source pointers) -- the reference's torch.cat never materialises."""
+    gamma|beta whose EPILOGUE is the GroupNorm apply with the modulation, the lerp and the channel concat (two source
+    pointers; ops.zerosft_conv, weights interleaved per 16 channels) -- neither the gamma|beta maps nor the reference's
+    torch.cat materialise, and the launch leaves the GroupNorm partials of its output for the consumer.  Where that
+    kernel does not take the operands (ops.zerosft_conv_supported): the convolution with concatenated weights, then
+    GroupNorm apply fused with the modulation."""
 
     def __init__(self, label_nc, norm_nc, concat_channels=0, norm=True, mask=False):
         super().__init__()
@@ -30,7 +33,12 @@ class ZeroSFT(nn.Module):
         self.zero_conv = Linear(label_nc, norm_nc, conv1x1=True)
         self.pre_concat = bool(concat_channels != 0)
         self.mask = mask
+        self._c1 = concat_channels if concat_channels else norm_nc      # channels of the first GroupNorm source (h_ori, or h + zero_conv(c) alone)
         object.__setattr__(self, "_gb", Prep())
+        object.__setattr__(self, "_gbi", Prep())
+        # shapes at which `forward` could not take the fused launch although the shape half of the predicate held (a producer left no
+        # GroupNorm partials): control_side then produces the gamma|beta maps ahead again, as before
+        object.__setattr__(self, "_zs_miss", set())
 
     def _w_gamma_beta(self):
         srcs = (self.zero_mul.weight, self.zero_add.weight, self.zero_mul.bias, self.zero_add.bias)
@@ -38,11 +46,23 @@ class ZeroSFT(nn.Module):
             torch.cat([Wt.conv3x3_w(self.zero_mul.weight), Wt.conv3x3_w(self.zero_add.weight)], 0).contiguous(),
             torch.cat([Wt.f32(self.zero_mul.bias), Wt.f32(self.zero_add.bias)], 0).contiguous()))
 
+    def _w_gamma_beta_interleaved(self):
+        """zero_mul | zero_add as ONE convolution with rows interleaved per 16 channels (ops.zerosft_conv)."""
+        srcs = (self.zero_mul.weight, self.zero_add.weight, self.zero_mul.bias, self.zero_add.bias)
+        return self._gbi.get(srcs, lambda: Wt.interleave_zerosft(Wt.conv3x3_w(self.zero_mul.weight), Wt.conv3x3_w(self.zero_add.weight),
+                                                                 Wt.f32(self.zero_mul.bias), Wt.f32(self.zero_add.bias)))
+
     def control_side(self, c):
-        """gamma|beta maps: depend on the control feature only, so they can be produced ahead of the decoder (side stream)."""
+        """What depends on the control feature only, so that it can be produced ahead of the decoder (side stream): the gamma|beta
+        maps [B,H,W,2*Ccat] -- or, where the fused kernel will take this adapter, only the shared activation [B,H,W,128] (`forward` tells
+        the two apart by the channel count)."""
         ch = to_nhwc(c)
         m = self.mlp_shared[0]
         actv = ops.conv3x3(ch, m.w(), m.b32(), act=1)
+        B, H, W, Ca = actv.shape
+        if (B, H, W, actv.dtype) not in self._zs_miss and \
+                ops.zerosft_conv_supported(B, H, W, Ca, self.param_free_norm.num_channels, self._c1, actv.dtype, static=True):
+            return actv
         wgb, bgb = self._w_gamma_beta()
         return ops.conv3x3(actv, wgb, bgb)                                               # [B,H,W,2*Ccat]
 
@@ -59,13 +79,21 @@ class ZeroSFT(nn.Module):
         cs = control_scale if torch.is_tensor(control_scale) else float(control_scale)
         raw = hh if (torch.is_tensor(cs) or cs != 1.0) else None
         if h_ori is not None and self.pre_concat:
-            ho = to_nhwc(h_ori)
-            out = ops.groupnorm(ho, n.g32(), n.b32(), n.eps, x2=hz, mod_g=gb[..., :Ccat], mod_b=gb[..., Ccat:],
-                                control_scale=cs, x2raw=raw, part=gn_part_of(h_ori), part2=pz)
+            x1, x2, p1, p2, r1, r2 = to_nhwc(h_ori), hz, gn_part_of(h_ori), pz, None, raw
         else:
             assert h_ori is None, "h_ori without pre_concat is not built by LightGLVUNet"
-            out = ops.groupnorm(hz, n.g32(), n.b32(), n.eps, mod_g=gb[..., :Ccat], mod_b=gb[..., Ccat:],
-                                control_scale=cs, x1raw=raw, part=pz)
+            x1, x2, p1, p2, r1, r2 = hz, None, pz, None, raw, None
+        if gb.shape[-1] != 2 * Ccat:       # control_side left the activation only
+            if ops.zerosft_conv_supported(B, H, W, gb.shape[-1], Ccat, x1.shape[-1], gb.dtype, p1, p2):
+                wi, bi = self._w_gamma_beta_interleaved()
+                out, po = ops.zerosft_conv(gb, wi, bi, x1, n.g32(), n.b32(), n.eps, x2=x2, control_scale=cs, x1raw=r1, x2raw=r2,
+                                           part=p1, part2=p2)
+                return attach_gn_part(to_nchw(out), po)
+            self._zs_miss.add((B, H, W, gb.dtype))
+            wgb, bgb = self._w_gamma_beta()     # (a producer left no partials: the two launches after all, and from now on ahead of the decoder)
+            gb = ops.conv3x3(gb, wgb, bgb)
+        out = ops.groupnorm(x1, n.g32(), n.b32(), n.eps, x2=x2, mod_g=gb[..., :Ccat], mod_b=gb[..., Ccat:],
+                            control_scale=cs, x1raw=r1, x2raw=r2, part=p1, part2=p2)
         return to_nchw(out)
 
 

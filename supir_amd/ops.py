@@ -1178,6 +1178,83 @@ def conv3x3(x, w, bias=None, *, stride=1, pad=(1, 1), upsample=False, out_hw=Non
     return (out, part) if gn_part else out
 
 
+# ZeroSFT adapters: the gamma|beta convolution with the GroupNorm + modulation + control-scale lerp as its epilogue (csrc/gemm16.hip
+# gemm16_zsft_kernel) instead of conv3x3 + groupnorm(mod_g, mod_b) and a [tokens][2 C] map between them.  0: always the two launches
+USE_ZSFT_FUSED = _os.environ.get("SUPIR_ZSFT_FUSED", "1") != "0"
+_ZSFT_TILES = {33: 128, 34: 256}      # tile -> rows (the one-wave-column forms of the 128 x 160 / 256 x 160 tiles)
+
+
+def zerosft_conv_supported(B, H, W, Cin, C, C1, dtype, part=None, part2=None, static=False):
+    """True when ops.zerosft_conv takes these operands (same conditions as supir_gemm16_zsft_supported).  static=True: the shape half only
+    (ZeroSFT.control_side decides before the decoder operands exist); else also the producers' GroupNorm partials of x / x2.
+    False whenever the fp32 service is active, launches are being recorded (paired_run) or ops.conv3x3 / ops.groupnorm are not this
+    module's own (test stand-ins swap those entry points and do not know this op): the caller then takes the two-launch path."""
+    g = globals()
+    if not USE_ZSFT_FUSED or not USE_GEMM16 or not USE_GN_PARTS or dtype not in HALF_TYPES or _DEFER is not None:
+        return False
+    if g["conv3x3"] is not _REAL_CONV3X3 or g["groupnorm"] is not _REAL_GROUPNORM:
+        return False
+    if Cin % 64 or C % 320 or C1 <= 0 or C1 > C or C1 % 80 or (H * W) % 128 or not any(t in G16_TILES for t in _ZSFT_TILES):
+        return False
+    if static:
+        return True
+    if part is None or part.unit != 10 or part.C != C1 or part.buf.shape[0] != B:
+        return False
+    if C1 < C and (part2 is None or part2.unit != 10 or part2.C != C - C1 or part2.buf.shape[0] != B):
+        return False
+    return True
+
+
+def zerosft_conv(actv, w, bias, x, gamma, beta, eps, *, x2=None, control_scale=1.0, x1raw=None, x2raw=None, part=None, part2=None,
+                 out=None, tile=-1):
+    """out = GN(cat[x, x2]) * (conv3x3(actv, zero_mul) + 1) + conv3x3(actv, zero_add), lerped with cat[x1raw, x2raw] by control_scale
+    (a float, or a 1-element fp32 device tensor read by the kernel) -- SUPIR_v0.py:62-113 in ONE launch (supir_conv3x3_zerosft).
+    actv [B,H,W,Cin]; w [2C,3,3,Cin] / bias [2C] interleaved per 16 channels (weights.interleave_zerosft); part / part2 = GnPart of
+    x / x2.  Returns (out [B,H,W,C], GnPart of out or None).  Callers check zerosft_conv_supported first: a refused shape raises."""
+    DT = actv.dtype
+    lib = _lib.load(DT)
+    _check_dev(actv, w, x)
+    _no_defer("zerosft_conv")
+    dyn = _dyn_cell(control_scale, x.device)
+    B, H, W, Cin = actv.shape
+    _, _, lda = _rows_ld(actv)
+    _, C1, ld1 = _rows_ld(x)
+    C, ld2 = C1, 0
+    if x2 is not None:
+        _, C2, ld2 = _rows_ld(x2)
+        C = C1 + C2
+    assert DT in HALF_TYPES and all(t is None or t.dtype == DT for t in (w, x, x2, x1raw, x2raw, out))
+    assert w.shape == (2 * C, 3, 3, Cin) and w.is_contiguous() and bias.numel() == 2 * C and bias.dtype == torch.float32
+    assert gamma.numel() == C and gamma.dtype == torch.float32 and beta.dtype == torch.float32
+    if not zerosft_conv_supported(B, H, W, Cin, C, C1, DT, part, part2):
+        raise _lib.SupirHipError("ops.zerosft_conv: operands outside the fused kernel's shapes (check zerosft_conv_supported first)")
+    if out is None:
+        out = torch.empty(B, H, W, C, dtype=DT, device=x.device)
+    _, _, ldo = _rows_ld(out)
+    cs_f = 1.0 if dyn else float(control_scale)
+
+    def launch(t, outp=None, hints=None):
+        return lib.supir_conv3x3_zerosft(actv.data_ptr(), w.data_ptr(), bias.data_ptr(), (out if outp is None else outp).data_ptr(), B, H, W,
+                                         Cin, lda, C, ldo, x.data_ptr(), _p(x2), _p(x1raw), _p(x2raw), C1, ld1, ld2, gamma.data_ptr(),
+                                         beta.data_ptr(), eps, part.buf.data_ptr(), part.nchunk, 0 if part2 is None else part2.buf.data_ptr(),
+                                         0 if part2 is None else part2.nchunk, cs_f, control_scale.data_ptr() if dyn else None, t,
+                                         None if hints is None else _ct.byref(hints), _stream())
+
+    key = ("zsft", B, H, W, Cin, C, C1) + _k(DT)
+    cands = tuple(t for t, bm in _ZSFT_TILES.items() if t in G16_TILES and (H * W) % bm == 0 and Cin % (128 if t == 33 else 64) == 0)
+    if tile == -1:
+        tile = _autotune(key, cands, launch)
+        if tile not in cands:       # first met while a graph is being captured (nothing may be timed there): the larger tile
+            tile = cands[-1]
+    part_out = _gn_part_alloc(tile, B, H * W, C, x.device)
+    M = B * H * W
+    _issue(_Launch(None, lib, "supir_conv3x3_zerosft", launch, key=key, tkey=key, tile=tile, single_tile=tile, cands=cands, w=w, part=part_out,
+                   out=out, trace=("zerosft_conv", 2.0 * M * 2 * C * 9 * Cin, 2.0 * (M * Cin + 2 * C * 9 * Cin + (3 if (dyn or cs_f != 1.0) else 2) * M * C),
+                                   dict(M=M, N=2 * C, K=9 * Cin, tile=tile)),
+                   keep=(actv, w, bias, x, x2, x1raw, x2raw, gamma, beta, part, part2, out, part_out, control_scale if dyn else None)))
+    return out, part_out
+
+
 # --------------------------------------------------------------------------------------------- attention
 def flash_attn(q, k, vt, B, H, Tq, Tk, out=None, causal=False):
     """q [B,Tq,>=H*64] k [B,Tk,>=H*64] (views with row stride), vt [B,H*64,Tpad]; returns [B,Tq,H*64].
@@ -1791,3 +1868,7 @@ def downsample_nearest_exact_affine(x, iy, ix, mom_old, mom_new):
     _lib.check(rc, "supir_downsample_nearest_exact_affine", lib)
     _rec("downsample_nearest_exact_affine", 0, 8.0 * N * C * OH * OW, ev)
     return out
+
+
+# the entry points test stand-ins swap (tests/torch_ops.py, tests/fake_ops.py): zerosft_conv_supported answers False unless these are in place
+_REAL_CONV3X3, _REAL_GROUPNORM = conv3x3, groupnorm

@@ -98,6 +98,18 @@ def interleave_geglu(w, b, block=32):
     return wi, bi
 
 
+def interleave_zerosft(w_mul, w_add, b_mul, b_add, block=16):
+    """ZeroSFT zero_mul / zero_add in kernel layout ([C, 3, 3, Cin] each, biases [C]) -> ONE convolution [2C, 3, 3, Cin] + bias [2C] with
+    the rows interleaved in blocks of `block`: row 2 * block * i + r = zero_mul row block * i + r, row 2 * block * i + block + r = zero_add
+    row block * i + r (r < block) -- one lane's fragment pair of the 16x16x32-MFMA tiles holds gamma and beta of the same output channel
+    (supir_conv3x3_zerosft)."""
+    c = w_mul.shape[0]
+    assert w_add.shape == w_mul.shape and c % block == 0
+    wi = torch.stack([w_mul.reshape(c // block, block, -1), w_add.reshape(c // block, block, -1)], dim=1).reshape(2 * c, *w_mul.shape[1:]).contiguous()
+    bi = torch.stack([b_mul.reshape(c // block, block), b_add.reshape(c // block, block)], dim=1).reshape(2 * c).contiguous()
+    return wi, bi
+
+
 def fold_layernorm(w, bias, gamma, beta):
     """LayerNorm folded into the following Linear: returns (W' = bf16(gamma (.) W) [N,K], colsum[n] = sum_k W'[n,k] (fp32,
     from the ROUNDED W' so that the mean term cancels exactly), b'[n] = bias[n] + sum_k beta[k] W[n,k]).
