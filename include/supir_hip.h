@@ -224,6 +224,20 @@ int supir_xattn_q_d64(const void* X, const void* Wq, const float* bias, const vo
                       int C, int ldx, int ldk, int ldvt, int ldo, const float* ln_stats, int ln_ld, int ln_slots, const float* ln_colsum,
                       float ln_eps, float scale, const supir_launch_hints* hints, void* stream);
 
+/* supir_xattn_q_d64 with a prompt PER REGION ("attention mode" regional prompting): K:[NR][Tk][ldk] and Vt:[NR][H*64][ldvt] are banks of
+ * NR text entries shared by all batch rows (entry e = the K / V^T of prompt e, same layout per entry as above), ids:[B][T] (uint8, device
+ * memory) names the entry of every query token, and token m's output is softmax(q_m K_e^T * scale) V_e over the Tk keys of its own entry
+ * e = ids[m] only.  One launch: a workgroup walks the entries between the smallest and largest id of its 128 rows through the same key
+ * ring; a tile of another entry leaves a token's running (max, sum, output) bit for bit as it was, so every output row equals the row
+ * supir_xattn_q_d64 produces with that token's entry as K / Vt.  Same shape rules as supir_xattn_q_d64 plus 1 <= NR <= 255
+ * (SUPIR_ERR_SHAPE otherwise, before any HIP call); a NULL ids or bank is SUPIR_ERR_ARG.  The VALUES of ids must lie in [0, NR): they
+ * are not checked (device memory).  Extends sgm/modules/attention.py:241-249 (to_q) + :273-277 / :357-359; per-region text context
+ * instead of the per-tile prompts of SUPIR/models/SUPIR_model.py:168-178. */
+int supir_xattn_q_d64_regions(const void* X, const void* Wq, const float* bias, const void* K, const void* Vt, const uint8_t* ids, int NR,
+                              void* O, int B, int H, int T, int Tk, int C, int ldx, int ldk, int ldvt, int ldo, const float* ln_stats,
+                              int ln_ld, int ln_slots, const float* ln_colsum, float ln_eps, float scale, const supir_launch_hints* hints,
+                              void* stream);
+
 /* softmax(Q K^T * scale) V for ONE head of dimension 512 without materialising the score matrix: the VAE mid-block attention
  * (sgm/modules/diffusionmodules/model.py:177-192 AttnBlock == :228-256 MemoryEfficientAttnBlock; SUPIR/utils/tilevae.py:276,335).
  * Q:[B][Tq][ldq], K:[B][Tk][ldk] (512 contiguous channels per token), Vt:[B][512][ldvt] = V transposed per batch

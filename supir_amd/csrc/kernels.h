@@ -107,6 +107,13 @@ struct XattnArgs {
     int gm, gn;             // 2-D XCD grid (launcher): XCD x owns token-block chunk x / gn and head chunk x % gn; gm = 0 -> 1-D ranges
 };
 
+// the regional form (supir_xattn_q_d64_regions): K / Vt are banks of NR entries ([NR][Tk][ldk] / [NR * H][64][ldvt]) shared by every
+// batch row, and token m attends to the keys of entry ids[m] only
+struct XattnRegArgs : XattnArgs {
+    const uint8_t* ids;     // [B * T], values in [0, NR) (the caller's contract: device memory)
+    int NR;
+};
+
 struct GnArgs {
     const bf16_t* x1;   // [B][HW][ld1], channels [0,C1)
     const bf16_t* x2;   // [B][HW][ld2], channels [C1,C)  (null when C1 == C)  -- the ZeroSFT / skip concat
@@ -176,6 +183,8 @@ int supir_attn_launch(const AttnArgs& a, hipStream_t st);
 int supir_attn_launch_n(const AttnArgs* a, int n, hipStream_t st);
 bool supir_xattn_q_supported(const XattnArgs& a);
 int supir_xattn_q_launch(const XattnArgs& a, hipStream_t st);
+bool supir_xattn_q_regions_supported(const XattnRegArgs& a);
+int supir_xattn_q_regions_launch(const XattnRegArgs& a, hipStream_t st);
 // attention_d512.hip: one head of dimension 512 (VAE mid block), 32-key tiles, 32 x 512 output tile per wave
 // (splits / workspace: the key-split form, see attention_d512.hip; workspace == nullptr -> one pass over all keys per workgroup)
 int supir_attn_d512_launch(const bf16_t* Q, const bf16_t* K, const bf16_t* Vt, bf16_t* O, int B, int Tq, int Tk, int ldq, int ldk,

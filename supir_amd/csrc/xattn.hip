@@ -40,8 +40,16 @@ constexpr int XQ_S = 3;
 constexpr int XQ_LOADS = 6;       // global->LDS instructions per wave and K step (4 token chunks + 2 weight chunks of 8 rows)
 constexpr int XQ_KV_LOADS = 4;    // per wave and key tile (K 64 x 64 + V^T 64 x 64 = 16 KB)
 
-__global__ __launch_bounds__(256, 2) void xattn_q_kernel(const XattnArgs p) {
-    __shared__ __attribute__((aligned(16))) char smem[XQ_S * XQ_STAGE];
+// REG = the regional form (supir_xattn_q_d64_regions, Args = XattnRegArgs): K / V^T are banks of NR text entries and every token attends
+// to the entry ids[token] names.  The projection half is the same; the attention half walks the entries e_lo .. e_hi its 128 rows name
+// (their min and max), each entry's nt key tiles, as ONE sequence of (e_hi - e_lo + 1) * nt tiles through the same ring.  In
+// S^T = K . Q^T a lane owns one token, so "this tile is of my entry" is a per-lane predicate over all 16 of its scores: where it is false
+// the lane takes the tile with alpha = exp2(0) = 1 and P = exp2(-inf - 0) = 0, which leaves (m_run, l_run, o) bit for bit as they were
+// (o * 1, l + 0, o + V . 0), and m_run, which is still -inf for a token whose entry comes later in the walk, never enters a subtraction.
+// A token's own tiles therefore see exactly the arithmetic of the plain kernel run on its entry alone.  A wave none of whose 32 tokens
+// is of the tile's entry skips the tile's arithmetic (not its barrier or its share of the loads).
+template <bool REG, class Args>
+__device__ __forceinline__ void xattn_q_body(const Args& p, char* smem) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, l31 = lane & 31;
     const int nqb = p.T >> 7;
@@ -62,6 +70,13 @@ __global__ __launch_bounds__(256, 2) void xattn_q_kernel(const XattnArgs p) {
     }
     const int qb = rq % nqb, b = rq / nqb;
     const size_t m0 = (size_t)b * p.T + (size_t)qb * 128;
+    int id_own = 0, id_a = 0, id_b = 0;
+    if constexpr (REG) {
+        const uint8_t* idp = p.ids + m0;
+        id_own = idp[(tid >> 6) * 32 + (tid & 31)];    // this lane's token (both lane halves hold the same one)
+        id_a = idp[tid & 63];                          // every wave reduces all 128 ids itself: no LDS, no barrier
+        id_b = idp[64 + (tid & 63)];
+    }
 
     // ---- GEMM loader: wave w stages the 8-row chunks w, w + 4, ... of the token tile and of the head's weight rows (same scheme and
     // source-side XOR swizzle as gemm16.hip: physical 16-byte chunk c of a 128-byte row holds logical chunk c ^ ((row >> 1) & 7))
@@ -79,12 +94,25 @@ __global__ __launch_bounds__(256, 2) void xattn_q_kernel(const XattnArgs p) {
     };
     // ---- key-tile loader (attention.hip's): tile t -> a ring buffer: K rows at +0, V^T rows at +8192, 128 bytes per row, swizzled
     const int nt = (p.Tk + 63) >> 6;
-    const char* Kb = (const char*)(p.K + (size_t)b * p.Tk * p.ldk + h * 64);
-    const char* Vb = (const char*)(p.Vt + ((size_t)b * p.H + h) * 64 * p.ldvt);
+    const char* Kb0 = (const char*)(p.K + (size_t)(REG ? 0 : b) * p.Tk * p.ldk + h * 64);     // REG: entry 0 of the banks
+    const char* Vb0 = (const char*)(p.Vt + ((size_t)(REG ? 0 : b) * p.H + h) * 64 * p.ldvt);
     const int a_lrow = tid >> 3, a_lchunk = (tid & 7) ^ ((tid >> 4) & 7);
+    // REG: stage_kv calls come in walk order, so the (entry, key tile) of the next one is a running pair; its `t` argument is the flat index
+    int st_e = 0, st_t = 0;
     auto stage_kv = [&](int buf, int t) {
         char* sK = smem + buf * XQ_STAGE;
         char* sV = sK + 8192;
+        const char* Kb = Kb0;
+        const char* Vb = Vb0;
+        if constexpr (REG) {
+            t = st_t;
+            Kb += (size_t)st_e * p.Tk * p.ldk * 2;
+            Vb += (size_t)st_e * p.H * 64 * p.ldvt * 2;
+            if (++st_t == nt) {
+                st_t = 0;
+                ++st_e;
+            }
+        }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int r = i * 32 + a_lrow;
@@ -137,6 +165,24 @@ __global__ __launch_bounds__(256, 2) void xattn_q_kernel(const XattnArgs p) {
     const int sw = (l31 >> 1) & 7;
     const int x_row_off = (wave * 32 + l31) * 128;
     const int w_row_off = 16384 + l31 * 128;
+    // REG: entries e_lo .. e_hi named by the workgroup's rows (clamped into the bank: the values are the caller's contract, the reads
+    // stay inside it regardless); ntl = key tiles of the whole walk
+    int e_lo = 0, ntl = nt;
+    if constexpr (REG) {
+        int mn = id_a < id_b ? id_a : id_b, mx = id_a < id_b ? id_b : id_a;
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+            const int on = __shfl_xor(mn, d, 64), ox = __shfl_xor(mx, d, 64);
+            mn = on < mn ? on : mn;
+            mx = ox > mx ? ox : mx;
+        }
+        int e_hi = __builtin_amdgcn_readfirstlane(mx);
+        e_lo = __builtin_amdgcn_readfirstlane(mn);
+        e_hi = e_hi < p.NR ? e_hi : p.NR - 1;
+        e_lo = e_lo < e_hi ? e_lo : e_hi;
+        st_e = e_lo;
+        ntl = (e_hi - e_lo + 1) * nt;
+    }
     int buf = 0;
     auto kstep = [&]() {
         const char* sT = smem + buf * XQ_STAGE;
@@ -176,7 +222,7 @@ __global__ __launch_bounds__(256, 2) void xattn_q_kernel(const XattnArgs p) {
     xq_wait_vmcnt<XQ_KV_LOADS>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if (nt > 1) stage_kv(kv1, 1);
+    if (ntl > 1) stage_kv(kv1, 1);
     kstep();
 
     // ---- q -> bf16 B-operand fragments of S^T = K . Q^T: k block i = 2 cb + pp holds accumulator registers 8 pp .. 8 pp + 7
@@ -199,7 +245,7 @@ __global__ __launch_bounds__(256, 2) void xattn_q_kernel(const XattnArgs p) {
     // key tile 2 (long prompts): the buffer the last K step used is free from here on; a key tile ends at +16 KB of it, under the
     // prefetch dump at +20 KB
     const int kv2 = buf == 0 ? XQ_S - 1 : buf - 1;
-    if (nt > 2) stage_kv(kv2, 2);
+    if (ntl > 2) stage_kv(kv2, 2);
 
     // next-weight prefetch (supir_launch_hints): lines of a LATER launch's weight matrix pulled towards L2 / Infinity Cache; the 4 bytes
     // per lane land in the ring buffer the last K step used (free from here on; the output staging below stays under +18 KB)
@@ -224,21 +270,32 @@ __global__ __launch_bounds__(256, 2) void xattn_q_kernel(const XattnArgs p) {
     for (int r = 0; r < 16; ++r) o[0][r] = o[1][r] = 0.f;
     float m_run = -INFINITY, l_run = 0.f;
     int kvb = kv0;
-    for (int t = 0; t < nt; ++t) {
+    int cur_e = e_lo, cur_t = 0;     // REG: the (entry, key tile) of flat tile t
+    for (int t = 0; t < ntl; ++t) {
         if (t >= 2) {
             // streamed tile: every wave's share of tile t has landed, and every wave is past tile t - 1, whose predecessor's buffer
             // takes tile t + 1
             xq_wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-            if (t + 1 < nt) stage_kv(kvb + 1 == XQ_S ? 0 : kvb + 1, t + 1);
+            if (t + 1 < ntl) stage_kv(kvb + 1 == XQ_S ? 0 : kvb + 1, t + 1);
         }
         const char* sK = smem + kvb * XQ_STAGE;
         kvb = kvb + 1 == XQ_S ? 0 : kvb + 1;
         const char* sV = sK + 8192;
+        const int kt = REG ? cur_t : t;
+        bool mine = true;
+        if constexpr (REG) {
+            mine = id_own == cur_e;
+            if (++cur_t == nt) {
+                cur_t = 0;
+                ++cur_e;
+            }
+            if (__builtin_amdgcn_ballot_w64(mine) == 0) continue;      // wave-uniform: no token of this wave is of the tile's entry
+        }
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
-            const int k0 = t * 64 + hf * 32;
+            const int k0 = kt * 64 + hf * 32;
             if (k0 >= p.Tk) break;      // wave-uniform
             f32x16 s;
 #pragma unroll
@@ -254,12 +311,15 @@ __global__ __launch_bounds__(256, 2) void xattn_q_kernel(const XattnArgs p) {
             float mx = -INFINITY;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                if (k0 + 16 * (r >> 3) + 8 * half + (r & 7) >= p.Tk) s[r] = -INFINITY;
+                if ((REG && !mine) || k0 + 16 * (r >> 3) + 8 * half + (r & 7) >= p.Tk) s[r] = -INFINITY;
                 mx = fmaxf(mx, s[r]);
             }
-            mx = xq_xhalf_max(mx);           // finite: key k0 is valid for every query
-            const float m_new = fmaxf(m_run, mx);
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+            mx = xq_xhalf_max(mx);           // finite where `mine`: key k0 is valid for every query of the tile's entry
+            // not `mine` (REG only): both maxima read as 0, so alpha = exp2(0) = 1 and every P = exp2(-inf - 0) = 0; m_run (possibly
+            // still -inf) is neither subtracted nor replaced
+            const float m_old = (REG && !mine) ? 0.f : m_run;
+            const float m_new = (REG && !mine) ? 0.f : fmaxf(m_run, mx);
+            const float alpha = __builtin_amdgcn_exp2f(m_old - m_new);
             l_run *= alpha;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -280,7 +340,7 @@ __global__ __launch_bounds__(256, 2) void xattn_q_kernel(const XattnArgs p) {
                     const bf16x8 vf = *(const bf16x8*)(sV + df * 4096 + l31 * 128 + (((2 * (2 * hf + kb) + half) ^ vsw) * 16));
                     o[df] = SUPIR_MFMA_32x32x16(vf, pf[kb], o[df], 0, 0, 0);
                 }
-            m_run = m_new;
+            m_run = (REG && !mine) ? m_run : m_new;
         }
     }
 
@@ -310,6 +370,39 @@ __global__ __launch_bounds__(256, 2) void xattn_q_kernel(const XattnArgs p) {
     }
 }
 
+__global__ __launch_bounds__(256, 2) void xattn_q_kernel(const XattnArgs p) {
+    __shared__ __attribute__((aligned(16))) char smem[XQ_S * XQ_STAGE];
+    xattn_q_body<false>(p, smem);
+}
+
+__global__ __launch_bounds__(256, 2) void xattn_q_regions_kernel(const XattnRegArgs p) {
+    __shared__ __attribute__((aligned(16))) char smem[XQ_S * XQ_STAGE];
+    xattn_q_body<true>(p, smem);
+}
+
+// XCD partition: every XCD's L2 pulls its own copy of what its workgroups read.  1-D ranges with the heads fastest give an XCD
+// (blocks / 8) token tiles and every head's weight rows -- at (B 2, H 20, T 1024, C 1280) 0.65 MB of tokens and ALL 3.3 MB of W_q,
+// 35.8 MB fetched for 9.3 MB of operands (profiles/pmc_traffic.json, round 4).  A gm x gn grid of XCDs (token-block chunks x head
+// chunks) cuts that to (blocks / gm) x 128 x C + (H / gn) x 64 x C elements per XCD; pick the cheapest grid that divides both counts
+// (knob 5 = 1, tools: keep the 1-D ranges)
+void xq_pick_grid(XattnArgs& a) {
+    a.gm = a.gn = 0;
+    const int blocks = (a.T / 128) * a.B;
+    if (supir_debug_knob_value(5) != 1) {
+        double best = 0.0;
+        for (int gm = 8; gm >= 1; gm >>= 1) {
+            const int gn = 8 / gm;
+            if (blocks % gm || a.H % gn) continue;
+            const double cost = (double)(blocks / gm) * 128.0 + (double)(a.H / gn) * 64.0;     // x C x 2 bytes
+            if (a.gm == 0 || cost < best) {
+                best = cost;
+                a.gm = gm;
+                a.gn = gn;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 bool supir_xattn_q_supported(const XattnArgs& a) {
@@ -326,26 +419,20 @@ bool supir_xattn_q_supported(const XattnArgs& a) {
 int supir_xattn_q_launch(const XattnArgs& a_in, hipStream_t st) {
     if (!supir_xattn_q_supported(a_in)) return SUPIR_ERR_SHAPE;
     XattnArgs a = a_in;
-    // XCD partition: every XCD's L2 pulls its own copy of what its workgroups read.  1-D ranges with the heads fastest give an XCD
-    // (blocks / 8) token tiles and every head's weight rows -- at (B 2, H 20, T 1024, C 1280) 0.65 MB of tokens and ALL 3.3 MB of W_q,
-    // 35.8 MB fetched for 9.3 MB of operands (profiles/pmc_traffic.json, round 4).  A gm x gn grid of XCDs (token-block chunks x head
-    // chunks) cuts that to (blocks / gm) x 128 x C + (H / gn) x 64 x C elements per XCD; pick the cheapest grid that divides both counts
-    // (knob 5 = 1, tools: keep the 1-D ranges)
-    a.gm = a.gn = 0;
-    const int blocks = (a.T / 128) * a.B;
-    if (supir_debug_knob_value(5) != 1) {
-        double best = 0.0;
-        for (int gm = 8; gm >= 1; gm >>= 1) {
-            const int gn = 8 / gm;
-            if (blocks % gm || a.H % gn) continue;
-            const double cost = (double)(blocks / gm) * 128.0 + (double)(a.H / gn) * 64.0;     // x C x 2 bytes
-            if (a.gm == 0 || cost < best) {
-                best = cost;
-                a.gm = gm;
-                a.gn = gn;
-            }
-        }
-    }
+    xq_pick_grid(a);
     SUPIR_LAUNCH(xattn_q_kernel, dim3((a.T / 128) * a.H * a.B), dim3(256), 0, st, a);
+    return SUPIR_LAUNCH_STATUS();
+}
+
+bool supir_xattn_q_regions_supported(const XattnRegArgs& a) {
+    // the bank is addressed by entry instead of by batch row; every other rule is the plain kernel's
+    return supir_xattn_q_supported(a) && a.NR >= 1 && a.NR <= 255 && a.ids != nullptr;
+}
+
+int supir_xattn_q_regions_launch(const XattnRegArgs& a_in, hipStream_t st) {
+    if (!supir_xattn_q_regions_supported(a_in)) return SUPIR_ERR_SHAPE;
+    XattnRegArgs a = a_in;
+    xq_pick_grid(a);
+    SUPIR_LAUNCH(xattn_q_regions_kernel, dim3((a.T / 128) * a.H * a.B), dim3(256), 0, st, a);
     return SUPIR_LAUNCH_STATUS();
 }

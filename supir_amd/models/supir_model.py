@@ -122,20 +122,27 @@ class SUPIRModel(nn.Module):
                         s_noise=1.003, cfg_scale=4.0, seed=-1, num_samples=1, control_scale=1, color_fix_type="None",
                         use_linear_CFG=False, use_linear_control_scale=False, cfg_scale_start=1.0,
                         control_scale_start=0.0, cond=None, noises=None, return_intermediates=False, prompt_chunks=None,
-                        **kwargs):
+                        regions=None, **kwargs):
         """SUPIR_model.py:80-136.  `cond=(c, uc)` bypasses the text conditioner (a `crossattn` longer than 77 tokens, e.g. the
         [N, 154, 2048] of a two-chunk prompt, needs nothing else: every layer below takes the token count from the tensor);
         `prompt_chunks` (None: self.prompt_chunks) lets prompts use up to that many 75-token chunks instead of being cut at 77 tokens
         (prepare_condition); prompts are strings or token-id tensors [N, 77 n]; `noises` (dict with optional
         'posterior', 'init', 'steps') injects the RNG draws for parity runs (otherwise the sampler's churn noise comes from
-        torch.randn_like on the device generator exactly like the reference)."""
+        torch.randn_like on the device generator exactly like the reference).
+
+        `regions` (untiled samplers): a prompt per REGION of one image, in one untiled network call -- `p = [[p_0 ... p_{R-1}]]` (the
+        local-prompt form, batch size 1 as in the reference; num_samples > 1 repeats the map) or `cond=([c_0 ... c_{R-1}], uc)`, and
+        `regions` an integer map [h, w] on the latent grid with values in [0, R), or R latent boxes (h0, h1, w0, w1), later boxes over
+        earlier ones, covering every pixel (sampling.region_map; sampling.regions_from_tiles gives the partition that matches the tiled
+        samplers' windows).  Every text cross-attention restricts each token to its region's prompt; the pooled `vector`, the control
+        hint and the scales are global and come from region 0's conditioning."""
         assert color_fix_type in ["Wavelet", "AdaIn", "None"]
         N = len(x)
         if num_samples > 1:
             assert N == 1
             N = num_samples
             x = x.repeat(N, 1, 1, 1)
-            if p is not None:
+            if p is not None and regions is None:
                 p = p.repeat(N, 1) if torch.is_tensor(p) else p * N
         p_p = self.p_p if p_p == "default" else p_p
         n_p = self.n_p if n_p == "default" else n_p
@@ -154,9 +161,12 @@ class SUPIRModel(nn.Module):
         _z = self.encode_first_stage_with_denoise(x, use_sample=False)
         x_stage1 = self.decode_first_stage(_z)
         z_stage1 = self.encode_first_stage(x_stage1, noise=noises.get("posterior"))
-        if cond is None:
+        if cond is None and regions is None:
             assert len(x) == len(p)   # SUPIR_model.py:95
-        if cond is not None:
+        if regions is not None:
+            # a prompt per region, one untiled network call (see the docstring)
+            c, uc, regions = self._regional_condition(_z, p, p_p, n_p, N, cond, regions, prompt_chunks)
+        elif cond is not None:
             # (c a list: per-tile conditionings, as prepare_condition returns them for local prompts)
             c = [dict(cj, control=_z) for cj in cond[0]] if isinstance(cond[0], (list, tuple)) else dict(cond[0], control=_z)
             uc = dict(cond[1], control=_z)
@@ -169,7 +179,8 @@ class SUPIRModel(nn.Module):
         if "steps" in noises:   # parity runs: per-step churn noise instead of torch.randn_like (RestoreEDMSampler only)
             self.sampler.injected_step_noises = list(noises["steps"])
         _samples = self.sampler(denoiser, noised_z, cond=c, uc=uc, x_center=z_stage1, control_scale=control_scale,
-                                use_linear_control_scale=use_linear_control_scale, control_scale_start=control_scale_start)
+                                use_linear_control_scale=use_linear_control_scale, control_scale_start=control_scale_start,
+                                **({} if regions is None else {"regions": regions}))
         samples = self.decode_first_stage(_samples)
         if color_fix_type == "Wavelet":
             from ..utils.colorfix import wavelet_reconstruction
@@ -180,6 +191,31 @@ class SUPIRModel(nn.Module):
         if return_intermediates:
             return samples, dict(z=_z, x_stage1=x_stage1, z_stage1=z_stage1, samples=_samples)
         return samples
+
+    def _regional_condition(self, _z, p, p_p, n_p, N, cond, regions, prompt_chunks):
+        """batchify_sample(regions=...): the per-region conditionings (c_0 ... c_{R-1}), uc and the checked [h, w] map.  The prompts are
+        those of ONE image (`p = [[...]]` or `cond=([...], uc)`); with num_samples = N their rows are repeated N times."""
+        from ..modules import sampling
+        if isinstance(self.sampler, sampling._TileGroups):
+            raise ValueError("the tiled samplers take per-tile prompts (their windows are the regions), not `regions`")
+
+        def rows(t):
+            return t if (not torch.is_tensor(t) or t.shape[0] == N) else t[:1].repeat(N, *([1] * (t.dim() - 1)))
+
+        if cond is not None:
+            if not isinstance(cond[0], (list, tuple)):
+                raise ValueError("`regions` needs cond=([c_0 ... c_{R-1}], uc): one conditioning per region")
+            c, uc = [dict(cj) for cj in cond[0]], dict(cond[1])
+        else:
+            if p is None or torch.is_tensor(p) or len(p) != 1 or not isinstance(p[0], (list, tuple)):
+                raise ValueError("`regions` needs p = [[p_0 ... p_{R-1}]]: the prompts of the regions of one image")
+            if not 1 <= len(p[0]) <= sampling.MAX_REGIONS:
+                raise ValueError(f"regional prompts take 1 .. {sampling.MAX_REGIONS} regions, got {len(p[0])}")
+            c, uc = self.prepare_condition(_z[:1], [list(p[0])], p_p, n_p, 1, prompt_chunks=prompt_chunks)
+        m = sampling.region_map(regions, len(c), _z.shape[-2], _z.shape[-1])
+        c = [dict({k: rows(v) for k, v in cj.items()}, control=_z) for cj in c]
+        uc = dict({k: rows(v) for k, v in uc.items()}, control=_z)
+        return c, uc, m
 
     def init_tile_vae(self, encoder_tile_size=512, decoder_tile_size=64, fast_encoder=False, fast_decoder=False, color_fix=False,
                       tile_chunk=None):

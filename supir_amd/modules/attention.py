@@ -23,6 +23,63 @@ def _pad64(t):
     return (t + 63) // 64 * 64
 
 
+def level_region_ids(ids, H, W):
+    """Region ids of a transformer level: ids [B, h, w] on the latent grid -> [B, H * W] (uint8, contiguous) for the level's (H, W)
+    token grid, ds = h / H: token (y, x) takes the id of latent pixel (y ds + ds // 2, x ds + ds // 2)."""
+    B, h, w = ids.shape
+    if H <= 0 or W <= 0 or h % H or w % W or h // H != w // W:
+        raise ValueError(f"a region map of {h} x {w} latent pixels has no ids for a {H} x {W} token grid")
+    ds = h // H
+    return ids[:, ds // 2::ds, ds // 2::ds].reshape(B, H * W).contiguous()
+
+
+class RegionalContext:
+    """The text context of regional prompting, passed where a plain `context` tensor goes: `bank` [cap, Tk, D] holds one text
+    embedding per entry (entry 0 the unconditional prompt, entries 1 .. R the regions' prompts; `n` <= cap entries are in use) and
+    `ids` [B, h, w] (uint8, < n) names, on the latent grid, the entry every pixel of every network batch row attends to.  Every text
+    cross-attention (attn2 of a BasicTransformerBlock) then restricts each token to the keys of its own entry; a SpatialTransformer
+    asks level_ids(H, W) for the ids of its token grid, which are derived once per map and level and kept.
+
+    The buffers are persistent: load() copies another image's bank and map INTO them and rewrites every level's table in place, so
+    a captured hipGraph that points at them (ControlWrapper keeps one RegionalContext per shape for exactly that) serves every
+    image and every map."""
+
+    def __init__(self, bank, ids, n=None):
+        if bank.dim() != 3 or ids.dim() != 3 or ids.dtype != torch.uint8:
+            raise ValueError("RegionalContext takes a bank [entries, Tk, D] and a uint8 id map [B, h, w]")
+        self.bank, self.ids = bank, ids.contiguous()
+        self.n = int(bank.shape[0] if n is None else n)
+        if not 1 <= self.n <= bank.shape[0] or bank.shape[0] > 255:
+            raise ValueError(f"{self.n} entries in use of a bank of {bank.shape[0]} (at most 255)")
+        self._levels = {}
+        self._source = None
+
+    @property
+    def cap(self):
+        return int(self.bank.shape[0])
+
+    def level_ids(self, H, W):
+        t = self._levels.get((H, W))
+        if t is None:
+            t = self._levels[(H, W)] = level_region_ids(self.ids, H, W)
+        return t
+
+    def load(self, other):
+        """Take over the bank and the map of `other` (same shapes, other.n <= cap) in place; a no-op while `other` is unchanged."""
+        src = (other.bank, other.bank._version, other.ids, other.ids._version, other.n)
+        cur = self._source
+        if cur is not None and all(a is b if torch.is_tensor(a) else a == b for a, b in zip(cur, src)):
+            return
+        if other.n > self.cap or other.ids.shape != self.ids.shape or other.bank.shape[1:] != self.bank.shape[1:]:
+            raise ValueError("RegionalContext.load: another shape, or more entries than the bank holds")
+        self.bank[:other.n].copy_(other.bank[:other.n])
+        self.ids.copy_(other.ids)
+        for (H, W), t in self._levels.items():
+            t.copy_(level_region_ids(self.ids, H, W))
+        self.n = other.n
+        self._source = src
+
+
 class CrossAttention(nn.Module):
     """q = to_q(x), k/v = to_k/to_v(context or x), softmax(q k^T / sqrt(64)) v, to_out.0 (+bias).
     Head split 'b n (h d) -> b h n d' (attention.py:254) is the column layout the flash kernel reads directly."""
@@ -46,17 +103,23 @@ class CrossAttention(nn.Module):
         return self._qk.get((self.to_q.weight, self.to_k.weight),
                             lambda: torch.cat([Wt.linear_w(self.to_q.weight), Wt.linear_w(self.to_k.weight)], 0).contiguous())
 
-    def _context_kv(self, context):
+    def _context_kv(self, context, kind=None):
         """K [B,Tk,C] and V^T [B,C,Tpad] of a context tensor.  One cache entry PER CONTEXT SHAPE, keyed on tensor identity +
         version and refreshed IN PLACE: a captured hipGraph holds raw pointers to these buffers, so an entry is never
         reallocated or evicted once created (switching between batch sizes -- e.g. tile-batched and single-tile calls of the
-        tiled sampler -- alternates between entries instead of freeing the other graph's buffers)."""
+        tiled sampler -- alternates between entries instead of freeing the other graph's buffers).
+        kind="regions": `context` is the bank [cap, Tk, D] of a RegionalContext -- the same rule (ControlWrapper's persistent
+        RegionalContext of a shape is refreshed in place per image, so its K / V^T are recomputed into the same buffers), in entries
+        of their own: a plain context of batch size cap keeps other buffers.  The id tables of the levels follow the rule too
+        (RegionalContext.load)."""
         wk, wv = self.to_k.w(), self.to_v.w()
         cache = self._kv_cache
         if cache is None:
             cache = {}
             object.__setattr__(self, "_kv_cache", cache)
         key = (tuple(context.shape), context.device) + ops._k(cdt())   # fp16 scopes keep their own buffers (other element type)
+        if kind is not None:
+            key += (kind,)
         c = cache.get(key)
         if c is not None and c[0] is context and c[1] == context._version and c[2] is wk and c[3] is wv:
             return c[4], c[5]
@@ -97,12 +160,19 @@ class CrossAttention(nn.Module):
         if c is not None:
             self._kv_cache[key] = (None, -1) + tuple(c[2:])
 
-    def attend(self, x, context=None, residual=None, alpha=1.0, inplace=False):
-        """x [B,T,C] bf16 tokens -> to_out(attention) (* alpha) (+ residual); inplace writes into `residual`."""
+    def attend(self, x, context=None, residual=None, alpha=1.0, inplace=False, region_ids=None):
+        """x [B,T,C] bf16 tokens -> to_out(attention) (* alpha) (+ residual); inplace writes into `residual`.
+        region_ids [B,T] (with a RegionalContext as `context`): every token attends to its own entry of the bank (ops.attn_regions)."""
         B, T, C = x.shape
         H = self.heads
         inner = H * 64
-        if context is None:
+        if region_ids is not None:
+            q = ops.gemm(x, self.to_q.w())
+            kb, vtb = self._context_kv(context.bank, "regions")
+            # every entry of the bank's CAPACITY, not just the context.n in use: under graph replay this loop runs at capture only, and
+            # a later image may use more entries of the same buffers (the unused ones hold finite data no id selects)
+            a = ops.attn_regions(q, kb, vtb, region_ids, B, H, T, kb.shape[1])
+        elif context is None:
             qk = ops.gemm(x, self._w_qk())                      # [B,T,2*inner]
             vt = ops.gemm_t(x, self.to_v.w(), None, B, T, _pad64(T))
             a = ops.flash_attn(qk[:, :, :inner], qk[:, :, inner:], vt, B, H, T, T)
@@ -195,10 +265,11 @@ class BasicTransformerBlock(nn.Module):
 
         return self._fold.get(srcs, build)
 
-    def forward_fused(self, x, stats, context):
+    def forward_fused(self, x, stats, context, region_ids=None):
         """Token stream x [B,T,C] (updated in place) + the RowStats its producer emitted -> (x, RowStats).
         No LayerNorm launches: every norm is folded into the GEMM that consumes it (supir_gemm_bf16_ln); each residual
-        GEMM emits the row statistics the next norm needs."""
+        GEMM emits the row statistics the next norm needs.
+        region_ids [B,T] (with a RegionalContext as `context`): the text cross-attention is ops.xattn_q_regions, one launch."""
         f = self._folded()
         B, T, C = x.shape
         H = self.attn1.heads
@@ -228,7 +299,10 @@ class BasicTransformerBlock(nn.Module):
         if FINALIZE_STATS:
             stats = ops.rowstats_finalize(stats, C, e2)
         w, cs, b = f["q2"]
-        k, vt2 = self.attn2._context_kv(context)
+        if region_ids is not None:
+            k, vt2 = self.attn2._context_kv(context.bank, "regions")
+        else:
+            k, vt2 = self.attn2._context_kv(context)
         Tk = k.shape[1]
         st2 = stats
 
@@ -239,7 +313,10 @@ class BasicTransformerBlock(nn.Module):
         def xattn_fused():
             return ops.xattn_q(x, w, b, k, vt2, B, H, T, Tk, ln=st2, colsum=cs, ln_eps=e2)
 
-        if ops.xattn_q_supported(B, T, C, H, Tk):
+        if region_ids is not None:
+            # (a shape the kernel refuses walks every entry of the bank's capacity: see CrossAttention.attend)
+            a = ops.xattn_q_regions(x, w, b, k, vt2, region_ids, B, H, T, Tk, ln=st2, colsum=cs, ln_eps=e2)
+        elif ops.xattn_q_supported(B, T, C, H, Tk):
             # to_q + the attention over the text keys (77 per prompt chunk) as ONE launch where that is faster (timed once, outside graph capture)
             which = ops.choose(("xattn", B, T, C, H, Tk) + ops._k(x.dtype), (xattn_separate, xattn_fused), prefer=1)
             a = xattn_fused() if which == 1 else xattn_separate()
@@ -254,14 +331,16 @@ class BasicTransformerBlock(nn.Module):
         l2 = self.ff.net[2]
         return ops.gemm_ln(g, l2.w(), l2.b32(), residual=x, out=x, emit_stats=True)
 
-    def forward(self, x, context=None, additional_tokens=None, n_times_crossframe_attn_in_self=0, inplace=False):
+    def forward(self, x, context=None, additional_tokens=None, n_times_crossframe_attn_in_self=0, inplace=False, region_ids=None):
         """x [B,T,C] -> x + attn1(LN x) ... (attention.py:465-486). inplace=True updates the token stream in place
-        (SpatialTransformer owns it)."""
+        (SpatialTransformer owns it).  region_ids: as in forward_fused."""
+        if region_ids is not None and (self.disable_self_attn or self.attn2.is_self):
+            raise NotImplementedError("regional prompts need a block with self-attention and a text cross-attention")
         x = tokens_bf16(x)
         n = ops.layernorm(x, self.norm1.g32(), self.norm1.b32(), self.norm1.eps)
         x = self.attn1.attend(n, context if self.disable_self_attn else None, residual=x, inplace=inplace)
         n = ops.layernorm(x, self.norm2.g32(), self.norm2.b32(), self.norm2.eps, out=n)
-        x = self.attn2.attend(n, context, residual=x, inplace=True)
+        x = self.attn2.attend(n, context, residual=x, inplace=True, region_ids=region_ids)
         n = ops.layernorm(x, self.norm3.g32(), self.norm3.b32(), self.norm3.eps, out=n)
         return self.ff(n, residual=x, inplace=True)
 
@@ -291,16 +370,22 @@ class SpatialTransformer(nn.Module):
             context = context[0]
         xh = to_nhwc(x)
         B, H, W, C = xh.shape
+        ids = None
+        if isinstance(context, RegionalContext):
+            # a prompt per region: this level's id table (derived once per map and level, RegionalContext.level_ids)
+            ids = context.level_ids(H, W)
+            if ids.shape[0] != B:
+                raise ValueError(f"the region map has {ids.shape[0]} batch rows, the tokens {B}")
         n = ops.groupnorm(xh, self.norm.g32(), self.norm.b32(), self.norm.eps, part=gn_part_of(x))
         fused = FOLD_LAYERNORM and ops.has_fused(cdt()) and context is not None and all(
             (not b.disable_self_attn) and (not b.attn2.is_self) for b in self.transformer_blocks)
         if fused:
             t, stats = ops.gemm_ln(n.view(B, H * W, C), self.proj_in.w(), self.proj_in.b32(), emit_stats=True)
             for blk in self.transformer_blocks:
-                t, stats = blk.forward_fused(t, stats, context)
+                t, stats = blk.forward_fused(t, stats, context, ids)
         else:
             t = ops.gemm(n.view(B, H * W, C), self.proj_in.w(), self.proj_in.b32())
             for blk in self.transformer_blocks:
-                t = blk(t, context=context, inplace=True)
+                t = blk(t, context=context, inplace=True, region_ids=ids)
         out, po = ops.gemm(t, self.proj_out.w(), self.proj_out.b32(), residual=xh.view(B, H * W, C), rows_per_batch=H * W, gn_part=True)
         return attach_gn_part(to_nchw(out.view(B, H, W, C)), po)

@@ -156,6 +156,91 @@ class NoDynamicThresholding:
 
 _CAT_KEYS = ("vector", "crossattn", "concat", "control", "control_vector", "mask_x")
 
+MAX_REGIONS = 254     # bank entries are uint8 ids and entry 0 is the unconditional prompt (supir_xattn_q_d64_regions takes 1 .. 255 entries)
+
+
+class RegionSpec:
+    """Regional prompts as the untiled samplers carry them in cond["regions"] until the guider builds the network's RegionalContext:
+    `contexts` = the R regions' text embeddings [1, Tk, D] (one token count), `map` = [h, w] uint8 on the latent grid, values < R."""
+
+    def __init__(self, contexts, map):
+        self.contexts, self.map = list(contexts), map
+        self._built = None      # the RegionalContext built last and what it was built for (_regional_context): once per image
+
+
+def region_map(regions, R, h, w):
+    """`regions` of batchify_sample -> the [h, w] uint8 map of region indices on the latent grid.  An integer map (tensor / array) is
+    checked and taken as it is; a list of R boxes (h0, h1, w0, w1) is painted in order, later boxes over earlier ones, and must cover
+    every pixel.  ValueError: R != the number of prompts / boxes, another size than the latent's, more than MAX_REGIONS regions."""
+    if R < 1 or R > MAX_REGIONS:
+        raise ValueError(f"regional prompts take 1 .. {MAX_REGIONS} regions, got {R}")
+    if torch.is_tensor(regions) or isinstance(regions, np.ndarray):
+        m = torch.as_tensor(regions).detach().cpu()
+        if m.dim() != 2 or tuple(m.shape) != (h, w):
+            raise ValueError(f"the region map is {tuple(m.shape)}, the latent grid {(h, w)}")
+        if m.is_floating_point() or m.dtype == torch.bool:
+            raise ValueError("the region map holds integer region indices")
+        m = m.to(torch.int64)
+        if m.numel() and (int(m.min()) < 0 or int(m.max()) >= R):
+            raise ValueError(f"the region map names regions {int(m.min())} .. {int(m.max())}; there are {R} prompts")
+        return m.to(torch.uint8).contiguous()
+    boxes = [tuple(int(v) for v in b) for b in regions]
+    if len(boxes) != R or any(len(b) != 4 for b in boxes):
+        raise ValueError(f"{len(boxes)} region boxes (h0, h1, w0, w1) for {R} prompts")
+    m = torch.full((h, w), -1, dtype=torch.int64)
+    for r, (h0, h1, w0, w1) in enumerate(boxes):
+        if not (0 <= h0 < h1 <= h and 0 <= w0 < w1 <= w):
+            raise ValueError(f"region box {r} = {(h0, h1, w0, w1)} does not lie inside the {h} x {w} latent grid")
+        m[h0:h1, w0:w1] = r
+    if bool((m < 0).any()):
+        raise ValueError(f"{int((m < 0).sum())} latent pixels are covered by no region box")
+    return m.to(torch.uint8).contiguous()
+
+
+def regions_from_tiles(h, w, tile_size, tile_stride):
+    """The partition of an h x w latent that gives every pixel to the tile of _sliding_windows(h, w, tile_size, tile_stride) whose
+    centre is nearest (ties: the lower tile index): [h, w] int64, region r = tile r, so the captions written for the tiled samplers'
+    per-tile prompts (SUPIR_model.py:168-178) serve as regional prompts unchanged."""
+    tiles = _sliding_windows(h, w, tile_size, tile_stride)
+    yy = 2 * np.arange(h, dtype=np.int64)[None, :, None]
+    xx = 2 * np.arange(w, dtype=np.int64)[None, None, :]
+    cy = np.array([a + b - 1 for (a, b, _, _) in tiles], dtype=np.int64)[:, None, None]     # twice the centre: exact in integers
+    cx = np.array([c + d - 1 for (_, _, c, d) in tiles], dtype=np.int64)[:, None, None]
+    d2 = (yy - cy) ** 2 + (xx - cx) ** 2
+    return torch.from_numpy(np.argmin(d2, axis=0).astype(np.int64))      # numpy's argmin returns the first minimum
+
+
+def _regional_cond(cond, regions, x):
+    """The untiled samplers' regional form: cond = the list of R per-region conditionings (the tiled samplers' local-prompt form) and
+    `regions` = the [h, w] map -> region 0's conditioning (vector, control, ...: everything but the text stays global) with
+    cond["regions"] = RegionSpec for the guider's prepare_cond."""
+    if not isinstance(cond, (list, tuple)) or regions is None:
+        raise ValueError("regional prompts take `cond` as a list of per-region conditionings together with `regions`; "
+                         "a list alone is the tiled samplers' per-tile form")
+    b, _, h, w = x.shape
+    m = region_map(regions, len(cond), h, w)
+    ctxs = [cj["crossattn"] for cj in cond]
+    if any(c.dim() != 3 or c.shape[1:] != ctxs[0].shape[1:] for c in ctxs):
+        raise ValueError("every region's crossattn must have one shape [N, 77 n, D] (prepare_condition pads them to one chunk count)")
+    out = dict(cond[0])
+    out["regions"] = RegionSpec([c[:1] for c in ctxs], m)
+    return out
+
+
+def _regional_context(spec, uc_ctx, rows_uc, rows_c, device):
+    """RegionalContext of a network batch of rows_uc unconditional rows followed by rows_c conditional ones: bank = [uc; region prompts],
+    ids = 0 on the unconditional rows, 1 + r on the others."""
+    from .attention import RegionalContext
+    key = (uc_ctx, uc_ctx._version, rows_uc, rows_c, str(device))
+    if spec._built is not None and spec._built[0][0] is uc_ctx and spec._built[0][1:] == key[1:]:
+        return spec._built[1]       # prepare_inputs callers ask once per step: the same object keeps the wrapper's buffers as they are
+    bank = torch.cat([uc_ctx[:1].to(spec.contexts[0])] + spec.contexts, 0)
+    m = spec.map.to(device)
+    ids = torch.cat([torch.zeros((rows_uc,) + tuple(m.shape), dtype=torch.uint8, device=device),
+                     (m + 1)[None].expand(rows_c, -1, -1)], 0).contiguous()
+    spec._built = (key, RegionalContext(bank.contiguous(), ids))
+    return spec._built[1]
+
 
 class LinearCFG:
     def __init__(self, scale, scale_min=None, dyn_thresh_config=None):
@@ -175,6 +260,10 @@ class LinearCFG:
         for k in c:
             if k in _CAT_KEYS:
                 out[k] = torch.cat((uc[k], c[k]), 0)
+            elif k == "regions":
+                # regional prompts: the doubled batch's id map -- unconditional rows entry 0, conditional rows 1 + region
+                n = c["crossattn"].shape[0]
+                out[k] = _regional_context(c[k], uc["crossattn"], uc["crossattn"].shape[0], n, c["crossattn"].device)
             else:
                 assert c[k] == uc[k]
                 out[k] = c[k]
@@ -194,10 +283,13 @@ class IdentityGuider:
         return x
 
     def prepare_cond(self, c, uc):
-        return dict(c)
+        out = dict(c)
+        if "regions" in c:      # no unconditional rows: every row 1 + region (entry 0 keeps the bank's layout)
+            out["regions"] = _regional_context(c["regions"], (uc or c)["crossattn"], 0, c["crossattn"].shape[0], c["crossattn"].device)
+        return out
 
     def prepare_inputs(self, x, s, c, uc):
-        return x, s, dict(c)
+        return x, s, self.prepare_cond(c, uc)
 
 
 # ----------------------------------------------------------------------------------------------- samplers
@@ -336,7 +428,11 @@ class RestoreEDMSampler(BaseDiffusionSampler):
                                  float(nxt - sigma_hat), reps)
 
     def __call__(self, denoiser, x, cond, uc=None, num_steps=None, x_center=None, control_scale=1.0,
-                 use_linear_control_scale=False, control_scale_start=0.0):
+                 use_linear_control_scale=False, control_scale_start=0.0, regions=None):
+        """regions (with `cond` a list of R per-region conditionings): the [h, w] map of region indices on the latent grid, or R boxes
+        (region_map) -- every text cross-attention then restricts each token to its region's prompt, in ONE untiled network call."""
+        if regions is not None or isinstance(cond, (list, tuple)):
+            cond = _regional_cond(cond, regions, x)
         x, s_in, sigmas, num_sigmas, cond, uc, sf = self.prepare_sampling_loop(x, cond, uc, num_steps)
         cond_cat = self.guider.prepare_cond(cond, uc)            # constant over the loop: concat once
         inject = self.__dict__.pop("injected_step_noises", None)  # parity runs: the churn noise of every step, given
@@ -535,7 +631,9 @@ class TiledRestoreEDMSampler(_TileGroups, RestoreEDMSampler):
         self.tile_weights = None
 
     def __call__(self, denoiser, x, cond, uc=None, num_steps=None, x_center=None, control_scale=1.0,
-                 use_linear_control_scale=False, control_scale_start=0.0):
+                 use_linear_control_scale=False, control_scale_start=0.0, regions=None):
+        if regions is not None:
+            raise ValueError("the tiled samplers take per-tile prompts (their windows are the regions), not `regions`")
         use_local_prompt = isinstance(cond, list)
         self.__dict__["_rep_cache"] = {}   # the repeated-conditioning cache is per call (`static` below is rebuilt every call)
         b, _, h, w = x.shape
@@ -845,7 +943,10 @@ class RestoreDPMPP2MSampler(BaseDiffusionSampler):
                 net.end_schedule()
         return x
 
-    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, control_scale=1.0, **kwargs):
+    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, control_scale=1.0, regions=None, **kwargs):
+        """regions: as on RestoreEDMSampler."""
+        if regions is not None or isinstance(cond, (list, tuple)):
+            cond = _regional_cond(cond, regions, x)
         x, s_in, sigmas, num_sigmas, cond, uc, sf, smin, smax = self._karras(x, cond, uc, num_steps)
         cond_cat = self.guider.prepare_cond(cond, uc)
         noise_sampler = self.noise_sampler_cls(x, smin, smax)
@@ -871,8 +972,10 @@ class TiledRestoreDPMPP2MSampler(_TileGroups, RestoreDPMPP2MSampler):
         super().__init__(*args, **kwargs)
         self._init_tiling(tile_size, tile_stride, tile_batch, tile_parallel, process_group, tile_batch_local_prompts)
 
-    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, control_scale=1.0, **kwargs):
+    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, control_scale=1.0, regions=None, **kwargs):
         import torch.distributed as dist
+        if regions is not None:
+            raise ValueError("the tiled samplers take per-tile prompts (their windows are the regions), not `regions`")
         use_local_prompt = isinstance(cond, list)
         self.__dict__["_rep_cache"] = {}   # per call, like TiledRestoreEDMSampler's
         b, _, h, w = x.shape

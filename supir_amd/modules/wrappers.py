@@ -94,6 +94,9 @@ class ControlWrapper(nn.Module):
         self._sel_group = 0            # the group select_step announced
         # per-image bank of text K / V^T for the tiled samplers' per-tile prompts (prepare_context_bank)
         self._bank = None
+        # regional prompts (cond["regions"], a RegionalContext): one PERSISTENT RegionalContext per (map shape, bank shape, element
+        # type) that every call's bank and map are loaded into -- what the captured graphs of that shape point at (_regions_slot)
+        self._region_slots = {}
         # per-image control-scale schedule (prepare_schedule(..., control_scales) / select_step): a device table, the 4-byte cell the
         # ZeroSFT / ZeroCrossAttn kernels read (allocated once per device: captured graphs point at it) and the fp32 host copy
         self._cs_cell = None
@@ -288,6 +291,40 @@ class ControlWrapper(nn.Module):
                 self._bank_forget()
             self._bank = None
 
+    # ------------------------------------------------------------------ regional prompts
+    REGION_BANK_STEP = 4      # bank capacities are multiples of this: a later image with a few more or fewer regions fits the same buffers
+
+    def _regions_slot(self, reg):
+        """The persistent RegionalContext serving calls shaped like `reg`, holding reg's bank and map (loaded in place; nothing happens
+        while reg is unchanged, i.e. on every step of an image after the first).  The text K / V^T of the bank (per layer,
+        CrossAttention._context_kv(..., "regions")) and the id tables of the levels hang off its buffers, so one graph per shape serves
+        every image, every map and every region count up to the capacity; a bank that outgrows it gets a larger slot (and graph)."""
+        from .attention import RegionalContext
+        step = self.REGION_BANK_STEP
+        key = (tuple(reg.ids.shape), tuple(reg.bank.shape[1:]), reg.bank.dtype, reg.bank.device, Wt.cdt())
+        slot = self._region_slots.get(key)
+        if slot is None or slot.cap < reg.n:
+            cap = min(255, (reg.n + step - 1) // step * step)
+            slot = RegionalContext(reg.bank.new_zeros((cap,) + tuple(reg.bank.shape[1:])), torch.zeros_like(reg.ids), n=reg.n)
+            self._region_slots[key] = slot
+        slot.load(reg)
+        return slot
+
+    def _refresh_regions(self, slot, vec):
+        """Before a replay: the step-independent buffers a regional graph reads hold THIS call's conditioning -- the bank's text K / V^T
+        of every cross-attention layer and the label embedding, each recomputed in place only when its source changed (the id tables
+        were rewritten by RegionalContext.load)."""
+        for net in (self.control_model, self.diffusion_model):
+            for a in net.text_attentions():
+                a._context_kv(slot.bank, "regions")
+            net._label(vec)
+        self._regions_took_labels(vec)
+
+    def _regions_took_labels(self, vec):
+        """A regional call wrote the label buffers of vec's shape: plain graphs of that shape refresh before their next replay."""
+        for k in [k for k in self._resident if k[1] == tuple(vec.shape)]:
+            del self._resident[k]
+
     def _use_schedule(self, kwargs, B=None):
         """Consume the one-call announcement; switch both networks' tables (the ones prepared for batch B) on / off for this call.
         Returns the schedule entry that serves the call, or None."""
@@ -309,6 +346,9 @@ class ControlWrapper(nn.Module):
     # ------------------------------------------------------------------ eager
     def _forward_eager(self, x, t, c, control_scale, **kwargs):
         ctx, vec = c.get("crossattn", None), c.get("vector", None)
+        reg = c.get("regions", None)
+        if reg is not None:
+            ctx = reg                  # the networks' `context`: SpatialTransformer takes the regional branch
         ckw = dict(x=c.get("control", None), timesteps=t, xt=x, control_vector=c.get("control_vector", None),
                    mask_x=c.get("mask_x", None), context=ctx, y=vec)
         if self.overlap_branches and self._warm and x.is_cuda and not kwargs:
@@ -362,7 +402,10 @@ class ControlWrapper(nn.Module):
             out = self.diffusion_model(x, timesteps=t, context=ctx, y=vec, control=control, control_scale=control_scale,
                                        **kwargs)
             self._warm = True   # weight / context caches are now built (they are filled on the calling stream)
-        if ctx is not None and vec is not None:
+        if reg is not None:
+            if vec is not None:
+                self._regions_took_labels(vec)
+        elif ctx is not None and vec is not None:
             # this call (re)filled the shared text-K/V^T / label buffers with ITS conditioning: graphs of the same shape that
             # were captured with another prompt must refresh before their next replay (_forward_graph checks this token)
             self._resident[(tuple(ctx.shape), tuple(vec.shape), Wt.cdt())] = (ctx, ctx._version, vec, vec._version)
@@ -383,6 +426,11 @@ class ControlWrapper(nn.Module):
         # a dynamic control scale (device cell) is read by the kernels at run time: the key holds a marker instead of the value
         cs_key = ("dynamic", control_scale.data_ptr()) if torch.is_tensor(control_scale) else float(control_scale)
         key = (tuple(x.shape), cs_key, tuple(ctx.shape), tuple(vec.shape), Wt.cdt()) + ((sched[1:3],) if sched else ())
+        # regional prompts: the graph points at the buffers of the persistent RegionalContext of this shape (forward put it into c);
+        # neither the map nor the number of regions in use is part of the key
+        reg = c.get("regions")
+        if reg is not None:
+            key += (("regions", id(reg)),)
         g = self._graphs.get(key)
         # a call of the per-image context bank: its K / V^T rows are gathered instead of recomputed
         bank = self._bank_table(ctx, vec, sched)
@@ -404,6 +452,8 @@ class ControlWrapper(nn.Module):
                 self._bank_apply(bank, ctx, vec, claim=True)     # the warm-up passes read the bank's rows too
             sx, st, sc = x.clone(), t.clone(), ctl.clone()
             cond = {"crossattn": ctx, "vector": vec, "control": sc}
+            if reg is not None:
+                cond["regions"] = reg
             # warm-up on a side stream: fills the weight / text-KV / label caches OUTSIDE the capture
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
@@ -435,7 +485,9 @@ class ControlWrapper(nn.Module):
         rkey = (key[2], key[3], key[4])
         res = self._resident.get(rkey)
         stale = res is None or res[0] is not ctx or res[1] != ctx._version or res[2] is not vec or res[3] != vec._version
-        if stale and bank is not None:
+        if reg is not None:
+            self._refresh_regions(reg, vec)
+        elif stale and bank is not None:
             # (the label embedding is not read: the call's embeddings come out of the schedule's table)
             self._bank_apply(bank, ctx, vec, claim=False)
         elif stale:
@@ -487,6 +539,8 @@ class ControlWrapper(nn.Module):
                                      f"the call passes {control_scale}")
                 control_scale = self._cs_cell
             self._cs_row = None
+            if isinstance(c, dict) and c.get("regions") is not None:
+                c = dict(c, regions=self._regions_slot(c["regions"]))
             if self._graph_on and not kwargs and x.is_cuda and self.effective_dtype != torch.float32:
                 return self._forward_graph(x, t, c, control_scale, sched)
             if self._graph_on:

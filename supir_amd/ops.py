@@ -1333,6 +1333,70 @@ def xattn_q(x, wq, bias, k, vt, B, H, T, Tk, *, ln=None, colsum=None, ln_eps=1e-
     return out
 
 
+def xattn_q_regions_supported(B, T, C, H, Tk, NR):
+    """Shape predicate of supir_xattn_q_d64_regions (csrc/xattn.hip): the rules of xattn_q_supported plus a bank of 1 .. 255 entries."""
+    return xattn_q_supported(B, T, C, H, Tk) and 1 <= NR <= 255
+
+
+def attn_regions(q, k_bank, vt_bank, ids, B, H, T, Tk, entries=None):
+    """The plain form of regional text attention: q [B,T,H*64], banks k [NR,Tk,H*64] / vt [NR,H*64,Tpad], ids [B,T] uint8 -> [B,T,H*64],
+    token (b, t) attending to the Tk keys of entry ids[b, t] only.  The existing attention runs once per entry (`entries`: the entries
+    that occur, default every one of the bank) over ALL tokens and the ids select per token.  Any element type; nobody tunes it.
+    A caller whose launches may be captured into a graph that serves other id maps must walk every entry (the default)."""
+    NR = k_bank.shape[0]
+    sel = ids.reshape(B, T, 1)
+    out = None
+    for e in (range(NR) if entries is None else entries):
+        ke = k_bank[e:e + 1].expand(B, -1, -1).contiguous()
+        ve = vt_bank[e:e + 1].expand(B, -1, -1).contiguous()
+        a = flash_attn(q, ke, ve, B, H, T, Tk)
+        out = torch.where(sel == e, a, torch.zeros_like(a) if out is None else out)
+    return out
+
+
+def xattn_q_regions(x, wq, bias, k_bank, vt_bank, ids, B, H, T, Tk, *, ln=None, colsum=None, ln_eps=1e-5, out=None, entries=None):
+    """xattn_q with a prompt per region: k_bank [NR,Tk,H*64] / vt_bank [NR,H*64,Tpad] (CrossAttention.context_kv_bank) are shared by all
+    batch rows and ids [B,T] (uint8, values < NR) names the entry each token attends to; one launch of supir_xattn_q_d64_regions.
+    Shapes the kernel refuses, fp32 operands and the switch SUPIR_FUSED_XATTN=0 take the projection and attn_regions instead."""
+    DT = x.dtype
+    M, C, ldx = _rows_ld(x)
+    NR = k_bank.shape[0]
+    assert ids.dtype == torch.uint8 and ids.is_contiguous() and ids.numel() == B * T and M == B * T
+    assert k_bank.shape[1] == Tk and k_bank.dtype == DT and vt_bank.dtype == DT
+    if DT not in HALF_TYPES or not xattn_q_regions_supported(B, T, C, H, Tk, NR):
+        if ln is not None:
+            q = gemm_ln(x, wq, bias, ln=ln, colsum=colsum, ln_eps=ln_eps)
+        else:
+            q = gemm(x, wq, bias)
+        return attn_regions(q.view(B, T, H * 64), k_bank, vt_bank, ids, B, H, T, Tk, entries=entries)
+    lib = _lib.load(DT)
+    _check_dev(x, wq, k_bank, vt_bank, ids)
+    assert wq.shape == (H * 64, C) and wq.is_contiguous() and wq.dtype == DT
+    assert k_bank.stride(-1) == 1 and vt_bank.is_contiguous() and vt_bank.shape[1] == H * 64
+    ldk, ldvt = k_bank.stride(-2), vt_bank.shape[-1]
+    assert k_bank.stride(0) == Tk * ldk
+    if out is None:
+        out = torch.empty(B, T, H * 64, dtype=DT, device=x.device)
+    assert out.dtype == DT
+    _, _, ldo = _rows_ld(out)
+    ln_p, ln_ld, ln_slots = 0, 0, 0
+    if ln is not None:
+        ln_p, ln_ld, ln_slots = ln.buf.data_ptr(), ln.ld, ln.slots
+        assert colsum is not None and colsum.numel() == H * 64
+
+    def launch(t, outp=None, hints=None):
+        return lib.supir_xattn_q_d64_regions(x.data_ptr(), wq.data_ptr(), _p(bias), k_bank.data_ptr(), vt_bank.data_ptr(), ids.data_ptr(), NR,
+                                             (out if outp is None else outp).data_ptr(), B, H, T, Tk, C, ldx, ldk, ldvt, ldo, ln_p, ln_ld,
+                                             ln_slots, _p(colsum), ln_eps, 0.125, None if hints is None else _ct.byref(hints), _stream())
+
+    N = H * 64
+    _issue(_Launch(None, lib, "supir_xattn_q_d64_regions", launch, w=wq, out=out,
+                   trace=("xattn_q_regions", 2.0 * M * N * C + 4.0 * M * N * Tk, 2.0 * (M * C + N * C + M * N + 2 * NR * Tk * N),
+                          dict(B=B, H=H, T=T, Tk=Tk, C=C, NR=NR)),
+                   keep=(x, wq, bias, k_bank, vt_bank, ids, out, ln.buf if ln is not None else None, colsum)))
+    return out
+
+
 # VAE mid-block attention (one head, dim 512): supir_flash_attn_d512 never forms the score matrix; the materialised form (GEMM -> fp32
 # scores [T, T] -> softmax_rows -> GEMM) moves ~3 GB per call at T = 16 384 but runs on the tuned GEMM tiles.  Until round 4 the flash
 # kernel had B * T / 128 workgroups of one wave per SIMD and lost below 16 384 tokens (T = 4096: 391 us vs 93 us materialised,
