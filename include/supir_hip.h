@@ -238,6 +238,22 @@ int supir_xattn_q_d64_regions(const void* X, const void* Wq, const float* bias, 
                               int ln_ld, int ln_slots, const float* ln_colsum, float ln_eps, float scale, const supir_launch_hints* hints,
                               void* stream);
 
+/* supir_xattn_q_d64_regions with SOFT region weights: the same banks K:[NR][Tk][ldk] / Vt:[NR][H*64][ldvt], and instead of one entry per
+ * token wts:[B][NR][T] (float32, device memory; >= 0 and summing to 1 over the entries: the kernel does not renormalise) gives every
+ * token a weight per entry.  Token m's output is  sum_e wts[b][e][m] * softmax(q_m K_e^T * scale) V_e  -- one launch: a workgroup walks
+ * the entries span[b][m / 128][0] .. [1] (span:[B][T/128][2], uint8, device memory: the first and last entry with a non-zero weight in
+ * that 128-token block; both ends are clamped into [0, NR), so a wrong span gives wrong numbers, never a read outside the banks)
+ * through the same key ring, runs the plain kernel's online softmax per entry from a fresh state on the lanes whose weight is > 0,
+ * and adds the entry's w * o / l to a second fp32 accumulator after its last tile (kept in units of the token's first contributing
+ * entry's 1 / l, which the store applies).  One-hot weights give the rows of supir_xattn_q_d64_regions bit for bit.  Same shape rules
+ * and status codes as supir_xattn_q_d64_regions (SUPIR_ERR_SHAPE before any HIP call; a NULL wts, span or bank is SUPIR_ERR_ARG).  Extends sgm/modules/attention.py:241-249 (to_q) + :273-277 / :357-359; the weights
+ * play the part of the Gaussian tile weights the tiled samplers blend per-tile prompts with (SUPIR/models/SUPIR_model.py:168-178,
+ * sgm/modules/diffusionmodules/sampling.py:605, :656-657, :733), inside one untiled call. */
+int supir_xattn_q_d64_regions_soft(const void* X, const void* Wq, const float* bias, const void* K, const void* Vt, const float* wts,
+                                   const uint8_t* span, int NR, void* O, int B, int H, int T, int Tk, int C, int ldx, int ldk, int ldvt,
+                                   int ldo, const float* ln_stats, int ln_ld, int ln_slots, const float* ln_colsum, float ln_eps, float scale,
+                                   const supir_launch_hints* hints, void* stream);
+
 /* softmax(Q K^T * scale) V for ONE head of dimension 512 without materialising the score matrix: the VAE mid-block attention
  * (sgm/modules/diffusionmodules/model.py:177-192 AttnBlock == :228-256 MemoryEfficientAttnBlock; SUPIR/utils/tilevae.py:276,335).
  * Q:[B][Tq][ldq], K:[B][Tk][ldk] (512 contiguous channels per token), Vt:[B][512][ldvt] = V transposed per batch

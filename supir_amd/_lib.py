@@ -108,6 +108,8 @@ SIGNATURES.update({
     "supir_xattn_q_d64": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P, I, I, P, F, F, P, P],
     # X, Wq, bias, K bank, Vt bank, ids, NR, O, B, H, T, Tk, C, ldx, ldk, ldvt, ldo, ln_stats, ln_ld, ln_slots, ln_colsum, ln_eps, scale, hints, stream
     "supir_xattn_q_d64_regions": [P, P, P, P, P, P, I, P, I, I, I, I, I, I, I, I, I, P, I, I, P, F, F, P, P],
+    # X, Wq, bias, K bank, Vt bank, wts, span, NR, O, B, H, T, Tk, C, ldx, ldk, ldvt, ldo, ln_stats, ln_ld, ln_slots, ln_colsum, ln_eps, scale, hints, stream
+    "supir_xattn_q_d64_regions_soft": [P, P, P, P, P, P, P, I, P, I, I, I, I, I, I, I, I, I, P, I, I, P, F, F, P, P],
     "supir_gemm_grouped": [P, P, I, P],
     "supir_conv3x3_bf16_splitk": [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P],
     "supir_splitk_finalize": [P, I, I, I, P, I, P, I, P],

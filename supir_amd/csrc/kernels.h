@@ -114,6 +114,14 @@ struct XattnRegArgs : XattnArgs {
     int NR;
 };
 
+// the soft regional form (supir_xattn_q_d64_regions_soft): the same banks, and token m's output is the wts-weighted sum over the entries
+// of its attention to each entry's keys
+struct XattnSoftArgs : XattnArgs {
+    const float* wts;       // [B][NR][T], >= 0, summing to 1 over the entries (the caller's contract: device memory)
+    const uint8_t* span;    // [B][T / 128][2]: first and last entry with a non-zero weight in the 128-token block (clamped into the bank)
+    int NR;
+};
+
 struct GnArgs {
     const bf16_t* x1;   // [B][HW][ld1], channels [0,C1)
     const bf16_t* x2;   // [B][HW][ld2], channels [C1,C)  (null when C1 == C)  -- the ZeroSFT / skip concat
@@ -185,6 +193,8 @@ bool supir_xattn_q_supported(const XattnArgs& a);
 int supir_xattn_q_launch(const XattnArgs& a, hipStream_t st);
 bool supir_xattn_q_regions_supported(const XattnRegArgs& a);
 int supir_xattn_q_regions_launch(const XattnRegArgs& a, hipStream_t st);
+bool supir_xattn_q_soft_supported(const XattnSoftArgs& a);
+int supir_xattn_q_soft_launch(const XattnSoftArgs& a, hipStream_t st);
 // attention_d512.hip: one head of dimension 512 (VAE mid block), 32-key tiles, 32 x 512 output tile per wave
 // (splits / workspace: the key-split form, see attention_d512.hip; workspace == nullptr -> one pass over all keys per workgroup)
 int supir_attn_d512_launch(const bf16_t* Q, const bf16_t* K, const bf16_t* Vt, bf16_t* O, int B, int Tq, int Tk, int ldq, int ldk,

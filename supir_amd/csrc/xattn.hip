@@ -48,8 +48,25 @@ constexpr int XQ_KV_LOADS = 4;    // per wave and key tile (K 64 x 64 + V^T 64 x
 // (o * 1, l + 0, o + V . 0), and m_run, which is still -inf for a token whose entry comes later in the walk, never enters a subtraction.
 // A token's own tiles therefore see exactly the arithmetic of the plain kernel run on its entry alone.  A wave none of whose 32 tokens
 // is of the tile's entry skips the tile's arithmetic (not its barrier or its share of the loads).
-template <bool REG, class Args>
+//
+// XQ_SOFT = the soft regional form (supir_xattn_q_d64_regions_soft, Args = XattnSoftArgs): the same banks and the same walk, over the
+// entries span[0] .. span[1] of the workgroup's 128-token block, but a token carries a weight per entry (wts, one coalesced load per
+// entry and lane, fetched one entry ahead) and its output is the weighted sum of its attention to every entry.  Per entry the lanes
+// with w > 0 run the plain kernel's online softmax from a fresh (m_run, l_run, o); the lanes with w == 0 take the tiles as "not mine"
+// lanes do above and stay at (-inf, 0, 0).  After the entry's last tile every lane forms 1 / l (wave-uniform code: the cross-half
+// shuffle is under no per-lane branch), the w > 0 lanes add their contribution to wacc (the others nothing, by select: 0 * (1 / 0) is
+// NaN) and the state is reset.  wacc is kept in units of the token's FIRST contributing entry: w_scale = that entry's 1 / l, the
+// entry adds o * w and every later one o * (w / l / w_scale) (a rounded product, then the add; 1 / l lies in [1 / Tk, 1], so the
+// ratio is tame whatever the weights), and the epilogue stores wacc * w_scale through the very expression the other forms store
+// o * (1 / l) through.  With one-hot weights that is o * 1 and the same 1 / l: the regional form's row bit for bit in both element
+// types (the fp16 build fuses the product into the conversion, one rounding, which a sum of already rounded o / l could not
+// reproduce); a power-of-two mix of one prompt is exact likewise.  A wave with no weight on an entry skips its arithmetic and
+// finalisation.
+enum { XQ_PLAIN = 0, XQ_REGIONS = 1, XQ_SOFT = 2 };
+
+template <int MODE, class Args>
 __device__ __forceinline__ void xattn_q_body(const Args& p, char* smem) {
+    constexpr bool REG = MODE == XQ_REGIONS, SOFT = MODE == XQ_SOFT, BANK = MODE != XQ_PLAIN;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, l31 = lane & 31;
     const int nqb = p.T >> 7;
@@ -77,6 +94,16 @@ __device__ __forceinline__ void xattn_q_body(const Args& p, char* smem) {
         id_a = idp[tid & 63];                          // every wave reduces all 128 ids itself: no LDS, no barrier
         id_b = idp[64 + (tid & 63)];
     }
+    // SOFT: the walk's ends (clamped below) and this lane's weight row; w_nxt = the weight of the entry the walk reaches next
+    int sp_lo = 0, sp_hi = 0;
+    const float* wp = nullptr;
+    float w_cur = 0.f, w_nxt = 0.f, w_scale = 0.f;     // w_scale: 1 / l of the lane's first contributing entry (0: none yet)
+    if constexpr (SOFT) {
+        const uint8_t* sp = p.span + ((size_t)b * nqb + qb) * 2;
+        sp_lo = sp[0];
+        sp_hi = sp[1];
+        wp = p.wts + (size_t)b * p.NR * p.T + (size_t)qb * 128 + (tid >> 6) * 32 + (tid & 31);
+    }
 
     // ---- GEMM loader: wave w stages the 8-row chunks w, w + 4, ... of the token tile and of the head's weight rows (same scheme and
     // source-side XOR swizzle as gemm16.hip: physical 16-byte chunk c of a 128-byte row holds logical chunk c ^ ((row >> 1) & 7))
@@ -94,17 +121,17 @@ __device__ __forceinline__ void xattn_q_body(const Args& p, char* smem) {
     };
     // ---- key-tile loader (attention.hip's): tile t -> a ring buffer: K rows at +0, V^T rows at +8192, 128 bytes per row, swizzled
     const int nt = (p.Tk + 63) >> 6;
-    const char* Kb0 = (const char*)(p.K + (size_t)(REG ? 0 : b) * p.Tk * p.ldk + h * 64);     // REG: entry 0 of the banks
-    const char* Vb0 = (const char*)(p.Vt + ((size_t)(REG ? 0 : b) * p.H + h) * 64 * p.ldvt);
+    const char* Kb0 = (const char*)(p.K + (size_t)(BANK ? 0 : b) * p.Tk * p.ldk + h * 64);     // REG / SOFT: entry 0 of the banks
+    const char* Vb0 = (const char*)(p.Vt + ((size_t)(BANK ? 0 : b) * p.H + h) * 64 * p.ldvt);
     const int a_lrow = tid >> 3, a_lchunk = (tid & 7) ^ ((tid >> 4) & 7);
-    // REG: stage_kv calls come in walk order, so the (entry, key tile) of the next one is a running pair; its `t` argument is the flat index
+    // REG / SOFT: stage_kv calls come in walk order, so the (entry, key tile) of the next one is a running pair; its `t` argument is the flat index
     int st_e = 0, st_t = 0;
     auto stage_kv = [&](int buf, int t) {
         char* sK = smem + buf * XQ_STAGE;
         char* sV = sK + 8192;
         const char* Kb = Kb0;
         const char* Vb = Vb0;
-        if constexpr (REG) {
+        if constexpr (BANK) {
             t = st_t;
             Kb += (size_t)st_e * p.Tk * p.ldk * 2;
             Vb += (size_t)st_e * p.H * 64 * p.ldvt * 2;
@@ -182,6 +209,17 @@ __device__ __forceinline__ void xattn_q_body(const Args& p, char* smem) {
         e_lo = e_lo < e_hi ? e_lo : e_hi;
         st_e = e_lo;
         ntl = (e_hi - e_lo + 1) * nt;
+    }
+    int e_last = 0;
+    if constexpr (SOFT) {
+        int e_hi = __builtin_amdgcn_readfirstlane(sp_hi);
+        e_lo = __builtin_amdgcn_readfirstlane(sp_lo);
+        e_hi = e_hi < p.NR ? e_hi : p.NR - 1;
+        e_lo = e_lo < e_hi ? e_lo : e_hi;
+        st_e = e_lo;
+        e_last = e_hi;
+        ntl = (e_hi - e_lo + 1) * nt;
+        w_nxt = wp[(size_t)e_lo * p.T];
     }
     int buf = 0;
     auto kstep = [&]() {
@@ -269,8 +307,13 @@ __device__ __forceinline__ void xattn_q_body(const Args& p, char* smem) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[0][r] = o[1][r] = 0.f;
     float m_run = -INFINITY, l_run = 0.f;
+    f32x16 wacc[SOFT ? 2 : 1];       // SOFT: the weighted sum over the entries finished so far
+    if constexpr (SOFT) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) wacc[0][r] = wacc[1][r] = 0.f;
+    }
     int kvb = kv0;
-    int cur_e = e_lo, cur_t = 0;     // REG: the (entry, key tile) of flat tile t
+    int cur_e = e_lo, cur_t = 0;     // REG / SOFT: the (entry, key tile) of flat tile t
     for (int t = 0; t < ntl; ++t) {
         if (t >= 2) {
             // streamed tile: every wave's share of tile t has landed, and every wave is past tile t - 1, whose predecessor's buffer
@@ -283,8 +326,24 @@ __device__ __forceinline__ void xattn_q_body(const Args& p, char* smem) {
         const char* sK = smem + kvb * XQ_STAGE;
         kvb = kvb + 1 == XQ_S ? 0 : kvb + 1;
         const char* sV = sK + 8192;
-        const int kt = REG ? cur_t : t;
+        const int kt = BANK ? cur_t : t;
         bool mine = true;
+        bool fin = false;            // SOFT: this is the entry's last tile
+        if constexpr (SOFT) {
+            if (cur_t == 0) {
+                w_cur = w_nxt;
+                const int e_n = cur_e < e_last ? cur_e + 1 : e_last;
+                w_nxt = wp[(size_t)e_n * p.T];
+            }
+            mine = w_cur > 0.f;
+            if (++cur_t == nt) {
+                cur_t = 0;
+                ++cur_e;
+                fin = true;
+            }
+            // wave-uniform: no token of this wave has weight on the entry -- every lane is at (-inf, 0, 0) and has nothing to add
+            if (__builtin_amdgcn_ballot_w64(mine) == 0) continue;
+        }
         if constexpr (REG) {
             mine = id_own == cur_e;
             if (++cur_t == nt) {
@@ -311,14 +370,14 @@ __device__ __forceinline__ void xattn_q_body(const Args& p, char* smem) {
             float mx = -INFINITY;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                if ((REG && !mine) || k0 + 16 * (r >> 3) + 8 * half + (r & 7) >= p.Tk) s[r] = -INFINITY;
+                if ((BANK && !mine) || k0 + 16 * (r >> 3) + 8 * half + (r & 7) >= p.Tk) s[r] = -INFINITY;
                 mx = fmaxf(mx, s[r]);
             }
             mx = xq_xhalf_max(mx);           // finite where `mine`: key k0 is valid for every query of the tile's entry
             // not `mine` (REG only): both maxima read as 0, so alpha = exp2(0) = 1 and every P = exp2(-inf - 0) = 0; m_run (possibly
             // still -inf) is neither subtracted nor replaced
-            const float m_old = (REG && !mine) ? 0.f : m_run;
-            const float m_new = (REG && !mine) ? 0.f : fmaxf(m_run, mx);
+            const float m_old = (BANK && !mine) ? 0.f : m_run;
+            const float m_new = (BANK && !mine) ? 0.f : fmaxf(m_run, mx);
             const float alpha = __builtin_amdgcn_exp2f(m_old - m_new);
             l_run *= alpha;
 #pragma unroll
@@ -340,7 +399,29 @@ __device__ __forceinline__ void xattn_q_body(const Args& p, char* smem) {
                     const bf16x8 vf = *(const bf16x8*)(sV + df * 4096 + l31 * 128 + (((2 * (2 * hf + kb) + half) ^ vsw) * 16));
                     o[df] = SUPIR_MFMA_32x32x16(vf, pf[kb], o[df], 0, 0, 0);
                 }
-            m_run = (REG && !mine) ? m_run : m_new;
+            m_run = (BANK && !mine) ? m_run : m_new;
+        }
+        if constexpr (SOFT) {
+            if (fin) {
+                // the entry is complete: wacc += o * (w / l in units of w_scale) as a rounded product (no contraction into the add),
+                // then a fresh state
+#pragma clang fp contract(off)
+                const float l_e = l_run + __shfl_xor(l_run, 32, 64);
+                const float inv_e = 1.0f / l_e;
+                const bool first = mine && w_scale == 0.f;
+                const float f_e = first ? w_cur : (w_cur * inv_e) / w_scale;      // not `mine`: 0 / 0 or 0 * inf, never used
+                w_scale = first ? inv_e : w_scale;
+#pragma unroll
+                for (int df = 0; df < 2; ++df)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float cn = o[df][r] * f_e;
+                        wacc[df][r] = wacc[df][r] + (mine ? cn : 0.f);
+                        o[df][r] = 0.f;
+                    }
+                m_run = -INFINITY;
+                l_run = 0.f;
+            }
         }
     }
 
@@ -357,7 +438,12 @@ __device__ __forceinline__ void xattn_q_body(const Args& p, char* smem) {
         for (int rg = 0; rg < 4; ++rg) {
             u16x4 ov;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) ov[e] = f2bf(o[df][rg * 4 + e] * inv);
+            for (int e = 0; e < 4; ++e) {
+                if constexpr (SOFT)
+                    ov[e] = f2bf(wacc[df][rg * 4 + e] * w_scale);
+                else
+                    ov[e] = f2bf(o[df][rg * 4 + e] * inv);
+            }
             *(u16x4*)(o_stage + l31 * ORS + (df * 32 + 8 * rg + 4 * half) * 2) = ov;
         }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -372,12 +458,17 @@ __device__ __forceinline__ void xattn_q_body(const Args& p, char* smem) {
 
 __global__ __launch_bounds__(256, 2) void xattn_q_kernel(const XattnArgs p) {
     __shared__ __attribute__((aligned(16))) char smem[XQ_S * XQ_STAGE];
-    xattn_q_body<false>(p, smem);
+    xattn_q_body<XQ_PLAIN>(p, smem);
 }
 
 __global__ __launch_bounds__(256, 2) void xattn_q_regions_kernel(const XattnRegArgs p) {
     __shared__ __attribute__((aligned(16))) char smem[XQ_S * XQ_STAGE];
-    xattn_q_body<true>(p, smem);
+    xattn_q_body<XQ_REGIONS>(p, smem);
+}
+
+__global__ __launch_bounds__(256, 2) void xattn_q_soft_kernel(const XattnSoftArgs p) {
+    __shared__ __attribute__((aligned(16))) char smem[XQ_S * XQ_STAGE];
+    xattn_q_body<XQ_SOFT>(p, smem);
 }
 
 // XCD partition: every XCD's L2 pulls its own copy of what its workgroups read.  1-D ranges with the heads fastest give an XCD
@@ -434,5 +525,17 @@ int supir_xattn_q_regions_launch(const XattnRegArgs& a_in, hipStream_t st) {
     XattnRegArgs a = a_in;
     xq_pick_grid(a);
     SUPIR_LAUNCH(xattn_q_regions_kernel, dim3((a.T / 128) * a.H * a.B), dim3(256), 0, st, a);
+    return SUPIR_LAUNCH_STATUS();
+}
+
+bool supir_xattn_q_soft_supported(const XattnSoftArgs& a) {
+    return supir_xattn_q_supported(a) && a.NR >= 1 && a.NR <= 255 && a.wts != nullptr && a.span != nullptr && !(((size_t)a.wts) & 3);
+}
+
+int supir_xattn_q_soft_launch(const XattnSoftArgs& a_in, hipStream_t st) {
+    if (!supir_xattn_q_soft_supported(a_in)) return SUPIR_ERR_SHAPE;
+    XattnSoftArgs a = a_in;
+    xq_pick_grid(a);
+    SUPIR_LAUNCH(xattn_q_soft_kernel, dim3((a.T / 128) * a.H * a.B), dim3(256), 0, st, a);
     return SUPIR_LAUNCH_STATUS();
 }

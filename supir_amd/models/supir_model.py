@@ -122,7 +122,7 @@ class SUPIRModel(nn.Module):
                         s_noise=1.003, cfg_scale=4.0, seed=-1, num_samples=1, control_scale=1, color_fix_type="None",
                         use_linear_CFG=False, use_linear_control_scale=False, cfg_scale_start=1.0,
                         control_scale_start=0.0, cond=None, noises=None, return_intermediates=False, prompt_chunks=None,
-                        regions=None, **kwargs):
+                        regions=None, region_weights=None, region_feather=None, **kwargs):
         """SUPIR_model.py:80-136.  `cond=(c, uc)` bypasses the text conditioner (a `crossattn` longer than 77 tokens, e.g. the
         [N, 154, 2048] of a two-chunk prompt, needs nothing else: every layer below takes the token count from the tensor);
         `prompt_chunks` (None: self.prompt_chunks) lets prompts use up to that many 75-token chunks instead of being cut at 77 tokens
@@ -135,14 +135,20 @@ class SUPIRModel(nn.Module):
         `regions` an integer map [h, w] on the latent grid with values in [0, R), or R latent boxes (h0, h1, w0, w1), later boxes over
         earlier ones, covering every pixel (sampling.region_map; sampling.regions_from_tiles gives the partition that matches the tiled
         samplers' windows).  Every text cross-attention restricts each token to its region's prompt; the pooled `vector`, the control
-        hint and the scales are global and come from region 0's conditioning."""
+        hint and the scales are global and come from region 0's conditioning.
+
+        Soft region weights (same prompts, same samplers, still one network call): `region_weights` = a float tensor / array [R, h, w]
+        on the latent grid, >= 0, normalised per pixel (sampling.region_weights; sampling.region_weights_from_tiles gives the tiled
+        samplers' Gaussian blend weights), used WITHOUT `regions`; or `regions=map_or_boxes, region_feather=k`, the (2k + 1)^2 box
+        filter over the hard map (sampling.feather_regions; k = 0: the hard map as one-hot weights).  Every text cross-attention then
+        outputs the weighted sum over the regions of the token's attention to each region's prompt."""
         assert color_fix_type in ["Wavelet", "AdaIn", "None"]
         N = len(x)
         if num_samples > 1:
             assert N == 1
             N = num_samples
             x = x.repeat(N, 1, 1, 1)
-            if p is not None and regions is None:
+            if p is not None and regions is None and region_weights is None:
                 p = p.repeat(N, 1) if torch.is_tensor(p) else p * N
         p_p = self.p_p if p_p == "default" else p_p
         n_p = self.n_p if n_p == "default" else n_p
@@ -161,11 +167,19 @@ class SUPIRModel(nn.Module):
         _z = self.encode_first_stage_with_denoise(x, use_sample=False)
         x_stage1 = self.decode_first_stage(_z)
         z_stage1 = self.encode_first_stage(x_stage1, noise=noises.get("posterior"))
-        if cond is None and regions is None:
+        if region_feather is not None and regions is None:
+            raise ValueError("`region_feather` softens a hard map: it needs `regions`")
+        if region_weights is not None and regions is not None:
+            raise ValueError("regional prompts take `regions` (with `region_feather` to soften them) or `region_weights`, not both")
+        if region_feather is not None and int(region_feather) < 0:
+            raise ValueError(f"`region_feather` is {region_feather}: the radius cannot be negative")
+        regional = regions is not None or region_weights is not None
+        if cond is None and not regional:
             assert len(x) == len(p)   # SUPIR_model.py:95
-        if regions is not None:
+        if regional:
             # a prompt per region, one untiled network call (see the docstring)
-            c, uc, regions = self._regional_condition(_z, p, p_p, n_p, N, cond, regions, prompt_chunks)
+            c, uc, regions, region_weights = self._regional_condition(_z, p, p_p, n_p, N, cond, regions, prompt_chunks, region_weights,
+                                                                      region_feather)
         elif cond is not None:
             # (c a list: per-tile conditionings, as prepare_condition returns them for local prompts)
             c = [dict(cj, control=_z) for cj in cond[0]] if isinstance(cond[0], (list, tuple)) else dict(cond[0], control=_z)
@@ -180,7 +194,8 @@ class SUPIRModel(nn.Module):
             self.sampler.injected_step_noises = list(noises["steps"])
         _samples = self.sampler(denoiser, noised_z, cond=c, uc=uc, x_center=z_stage1, control_scale=control_scale,
                                 use_linear_control_scale=use_linear_control_scale, control_scale_start=control_scale_start,
-                                **({} if regions is None else {"regions": regions}))
+                                **({} if regions is None else {"regions": regions}),
+                                **({} if region_weights is None else {"region_weights": region_weights}))
         samples = self.decode_first_stage(_samples)
         if color_fix_type == "Wavelet":
             from ..utils.colorfix import wavelet_reconstruction
@@ -192,9 +207,10 @@ class SUPIRModel(nn.Module):
             return samples, dict(z=_z, x_stage1=x_stage1, z_stage1=z_stage1, samples=_samples)
         return samples
 
-    def _regional_condition(self, _z, p, p_p, n_p, N, cond, regions, prompt_chunks):
-        """batchify_sample(regions=...): the per-region conditionings (c_0 ... c_{R-1}), uc and the checked [h, w] map.  The prompts are
-        those of ONE image (`p = [[...]]` or `cond=([...], uc)`); with num_samples = N their rows are repeated N times."""
+    def _regional_condition(self, _z, p, p_p, n_p, N, cond, regions, prompt_chunks, region_weights=None, region_feather=None):
+        """batchify_sample(regions=...): the per-region conditionings (c_0 ... c_{R-1}), uc, the checked [h, w] map and None -- or, with
+        `region_weights` or `region_feather`, None and the checked soft weights [R, h, w].  The prompts are those of ONE image
+        (`p = [[...]]` or `cond=([...], uc)`); with num_samples = N their rows are repeated N times."""
         from ..modules import sampling
         if isinstance(self.sampler, sampling._TileGroups):
             raise ValueError("the tiled samplers take per-tile prompts (their windows are the regions), not `regions`")
@@ -212,10 +228,16 @@ class SUPIRModel(nn.Module):
             if not 1 <= len(p[0]) <= sampling.MAX_REGIONS:
                 raise ValueError(f"regional prompts take 1 .. {sampling.MAX_REGIONS} regions, got {len(p[0])}")
             c, uc = self.prepare_condition(_z[:1], [list(p[0])], p_p, n_p, 1, prompt_chunks=prompt_chunks)
-        m = sampling.region_map(regions, len(c), _z.shape[-2], _z.shape[-1])
+        m = wts = None
+        if region_weights is not None:
+            wts = sampling.region_weights(region_weights, len(c), _z.shape[-2], _z.shape[-1])
+        else:
+            m = sampling.region_map(regions, len(c), _z.shape[-2], _z.shape[-1])
+            if region_feather is not None:
+                m, wts = None, sampling.feather_regions(m, len(c), int(region_feather))
         c = [dict({k: rows(v) for k, v in cj.items()}, control=_z) for cj in c]
         uc = dict({k: rows(v) for k, v in uc.items()}, control=_z)
-        return c, uc, m
+        return c, uc, m, wts
 
     def init_tile_vae(self, encoder_tile_size=512, decoder_tile_size=64, fast_encoder=False, fast_decoder=False, color_fix=False,
                       tile_chunk=None):

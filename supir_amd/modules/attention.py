@@ -33,6 +33,31 @@ def level_region_ids(ids, H, W):
     return ids[:, ds // 2::ds, ds // 2::ds].reshape(B, H * W).contiguous()
 
 
+def region_span(wts):
+    """The walk bounds supir_xattn_q_d64_regions_soft takes: wts [B, NR, T] (T a multiple of 128) -> [B, T / 128, 2] uint8, the first and
+    the last entry with a non-zero weight anywhere in each 128-token block (torch ops on wts' device; a block with no weight at all,
+    which normalised weights never have, gets the single entry 0)."""
+    B, NR, T = wts.shape
+    nz = (wts > 0).view(B, NR, T // 128, 128).any(-1)                        # [B, NR, blocks]
+    e = torch.arange(NR, device=wts.device).view(1, NR, 1)
+    lo = torch.where(nz, e, NR).amin(1).clamp_(max=NR - 1)
+    hi = torch.where(nz, e, 0).amax(1)
+    return torch.stack((torch.minimum(lo, hi), hi), -1).to(torch.uint8).contiguous()
+
+
+def level_region_weights(weights, H, W):
+    """Soft region weights of a transformer level: weights [B, cap, h, w] (float32) on the latent grid -> (wts [B, cap, H * W] float32
+    contiguous, span [B, H * W / 128, 2] uint8) for the level's (H, W) token grid, by the sampling rule of level_region_ids (token
+    (y, x) reads latent pixel (y ds + ds // 2, x ds + ds // 2)), so one-hot weights mean at every level what the hard ids mean.
+    span is None where H * W is no multiple of 128: the kernel refuses that level and the plain form needs no span."""
+    B, cap, h, w = weights.shape
+    if H <= 0 or W <= 0 or h % H or w % W or h // H != w // W:
+        raise ValueError(f"region weights of {h} x {w} latent pixels have no values for a {H} x {W} token grid")
+    ds = h // H
+    wts = weights[:, :, ds // 2::ds, ds // 2::ds].reshape(B, cap, H * W).contiguous()
+    return wts, (region_span(wts) if (H * W) % 128 == 0 else None)
+
+
 class RegionalContext:
     """The text context of regional prompting, passed where a plain `context` tensor goes: `bank` [cap, Tk, D] holds one text
     embedding per entry (entry 0 the unconditional prompt, entries 1 .. R the regions' prompts; `n` <= cap entries are in use) and
@@ -42,12 +67,22 @@ class RegionalContext:
 
     The buffers are persistent: load() copies another image's bank and map INTO them and rewrites every level's table in place, so
     a captured hipGraph that points at them (ControlWrapper keeps one RegionalContext per shape for exactly that) serves every
-    image and every map."""
+    image and every map.
 
-    def __init__(self, bank, ids, n=None):
+    Soft region weights: `weights` [B, cap, h, w] (float32, >= 0, summing to 1 over the entries at every pixel, zero on entries >= n)
+    gives every pixel a weight per entry; every text cross-attention then outputs the weighted sum of the token's attention to each
+    entry (ops.xattn_q_regions_soft), `ids` only records the heaviest entry, and a SpatialTransformer asks level_weights(H, W) for
+    the level's (wts, span).  A context is hard or soft for life: load() takes only its own kind."""
+
+    def __init__(self, bank, ids, n=None, weights=None):
         if bank.dim() != 3 or ids.dim() != 3 or ids.dtype != torch.uint8:
             raise ValueError("RegionalContext takes a bank [entries, Tk, D] and a uint8 id map [B, h, w]")
+        if weights is not None and (weights.dtype != torch.float32 or weights.dim() != 4 or weights.shape[1] != bank.shape[0]
+                                    or (weights.shape[0],) + tuple(weights.shape[2:]) != tuple(ids.shape)):
+            raise ValueError("RegionalContext takes float32 weights [B, entries, h, w] next to the id map [B, h, w]")
         self.bank, self.ids = bank, ids.contiguous()
+        self.weights = None if weights is None else weights.contiguous()
+        self._wlevels = {}
         self.n = int(bank.shape[0] if n is None else n)
         if not 1 <= self.n <= bank.shape[0] or bank.shape[0] > 255:
             raise ValueError(f"{self.n} entries in use of a bank of {bank.shape[0]} (at most 255)")
@@ -64,9 +99,20 @@ class RegionalContext:
             t = self._levels[(H, W)] = level_region_ids(self.ids, H, W)
         return t
 
+    def level_weights(self, H, W):
+        """(wts [B, cap, H * W], span [B, H * W / 128, 2] or None) of a soft context: level_region_weights, once per map and level."""
+        t = self._wlevels.get((H, W))
+        if t is None:
+            t = self._wlevels[(H, W)] = level_region_weights(self.weights, H, W)
+        return t
+
     def load(self, other):
         """Take over the bank and the map of `other` (same shapes, other.n <= cap) in place; a no-op while `other` is unchanged."""
+        if (other.weights is None) != (self.weights is None):
+            raise ValueError("RegionalContext.load: a hard context takes a hard one, a soft context a soft one")
         src = (other.bank, other.bank._version, other.ids, other.ids._version, other.n)
+        if other.weights is not None:
+            src += (other.weights, other.weights._version)
         cur = self._source
         if cur is not None and all(a is b if torch.is_tensor(a) else a == b for a, b in zip(cur, src)):
             return
@@ -76,6 +122,15 @@ class RegionalContext:
         self.ids.copy_(other.ids)
         for (H, W), t in self._levels.items():
             t.copy_(level_region_ids(self.ids, H, W))
+        if self.weights is not None:
+            # other's bank may be smaller than this one's capacity: entries >= other.n carry no weight
+            self.weights[:, :other.n].copy_(other.weights[:, :other.n])
+            self.weights[:, other.n:].zero_()
+            for (H, W), (wts, span) in self._wlevels.items():
+                nw, ns = level_region_weights(self.weights, H, W)
+                wts.copy_(nw)
+                if span is not None:
+                    span.copy_(ns)
         self.n = other.n
         self._source = src
 
@@ -160,13 +215,18 @@ class CrossAttention(nn.Module):
         if c is not None:
             self._kv_cache[key] = (None, -1) + tuple(c[2:])
 
-    def attend(self, x, context=None, residual=None, alpha=1.0, inplace=False, region_ids=None):
+    def attend(self, x, context=None, residual=None, alpha=1.0, inplace=False, region_ids=None, region_weights=None):
         """x [B,T,C] bf16 tokens -> to_out(attention) (* alpha) (+ residual); inplace writes into `residual`.
-        region_ids [B,T] (with a RegionalContext as `context`): every token attends to its own entry of the bank (ops.attn_regions)."""
+        region_ids [B,T] (with a RegionalContext as `context`): every token attends to its own entry of the bank (ops.attn_regions).
+        region_weights (wts [B,cap,T], span) instead: the weighted sum over the entries (ops.attn_regions_soft)."""
         B, T, C = x.shape
         H = self.heads
         inner = H * 64
-        if region_ids is not None:
+        if region_weights is not None:
+            q = ops.gemm(x, self.to_q.w())
+            kb, vtb = self._context_kv(context.bank, "regions")
+            a = ops.attn_regions_soft(q, kb, vtb, region_weights[0], B, H, T, kb.shape[1])      # (every entry: as below)
+        elif region_ids is not None:
             q = ops.gemm(x, self.to_q.w())
             kb, vtb = self._context_kv(context.bank, "regions")
             # every entry of the bank's CAPACITY, not just the context.n in use: under graph replay this loop runs at capture only, and
@@ -265,11 +325,12 @@ class BasicTransformerBlock(nn.Module):
 
         return self._fold.get(srcs, build)
 
-    def forward_fused(self, x, stats, context, region_ids=None):
+    def forward_fused(self, x, stats, context, region_ids=None, region_weights=None):
         """Token stream x [B,T,C] (updated in place) + the RowStats its producer emitted -> (x, RowStats).
         No LayerNorm launches: every norm is folded into the GEMM that consumes it (supir_gemm_bf16_ln); each residual
         GEMM emits the row statistics the next norm needs.
-        region_ids [B,T] (with a RegionalContext as `context`): the text cross-attention is ops.xattn_q_regions, one launch."""
+        region_ids [B,T] (with a RegionalContext as `context`): the text cross-attention is ops.xattn_q_regions, one launch;
+        region_weights (wts [B,cap,T], span) instead: ops.xattn_q_regions_soft, one launch."""
         f = self._folded()
         B, T, C = x.shape
         H = self.attn1.heads
@@ -299,7 +360,7 @@ class BasicTransformerBlock(nn.Module):
         if FINALIZE_STATS:
             stats = ops.rowstats_finalize(stats, C, e2)
         w, cs, b = f["q2"]
-        if region_ids is not None:
+        if region_ids is not None or region_weights is not None:
             k, vt2 = self.attn2._context_kv(context.bank, "regions")
         else:
             k, vt2 = self.attn2._context_kv(context)
@@ -313,7 +374,9 @@ class BasicTransformerBlock(nn.Module):
         def xattn_fused():
             return ops.xattn_q(x, w, b, k, vt2, B, H, T, Tk, ln=st2, colsum=cs, ln_eps=e2)
 
-        if region_ids is not None:
+        if region_weights is not None:
+            a = ops.xattn_q_regions_soft(x, w, b, k, vt2, region_weights[0], region_weights[1], B, H, T, Tk, ln=st2, colsum=cs, ln_eps=e2)
+        elif region_ids is not None:
             # (a shape the kernel refuses walks every entry of the bank's capacity: see CrossAttention.attend)
             a = ops.xattn_q_regions(x, w, b, k, vt2, region_ids, B, H, T, Tk, ln=st2, colsum=cs, ln_eps=e2)
         elif ops.xattn_q_supported(B, T, C, H, Tk):
@@ -331,16 +394,17 @@ class BasicTransformerBlock(nn.Module):
         l2 = self.ff.net[2]
         return ops.gemm_ln(g, l2.w(), l2.b32(), residual=x, out=x, emit_stats=True)
 
-    def forward(self, x, context=None, additional_tokens=None, n_times_crossframe_attn_in_self=0, inplace=False, region_ids=None):
+    def forward(self, x, context=None, additional_tokens=None, n_times_crossframe_attn_in_self=0, inplace=False, region_ids=None,
+                region_weights=None):
         """x [B,T,C] -> x + attn1(LN x) ... (attention.py:465-486). inplace=True updates the token stream in place
-        (SpatialTransformer owns it).  region_ids: as in forward_fused."""
-        if region_ids is not None and (self.disable_self_attn or self.attn2.is_self):
+        (SpatialTransformer owns it).  region_ids / region_weights: as in forward_fused."""
+        if (region_ids is not None or region_weights is not None) and (self.disable_self_attn or self.attn2.is_self):
             raise NotImplementedError("regional prompts need a block with self-attention and a text cross-attention")
         x = tokens_bf16(x)
         n = ops.layernorm(x, self.norm1.g32(), self.norm1.b32(), self.norm1.eps)
         x = self.attn1.attend(n, context if self.disable_self_attn else None, residual=x, inplace=inplace)
         n = ops.layernorm(x, self.norm2.g32(), self.norm2.b32(), self.norm2.eps, out=n)
-        x = self.attn2.attend(n, context, residual=x, inplace=True, region_ids=region_ids)
+        x = self.attn2.attend(n, context, residual=x, inplace=True, region_ids=region_ids, region_weights=region_weights)
         n = ops.layernorm(x, self.norm3.g32(), self.norm3.b32(), self.norm3.eps, out=n)
         return self.ff(n, residual=x, inplace=True)
 
@@ -370,8 +434,13 @@ class SpatialTransformer(nn.Module):
             context = context[0]
         xh = to_nhwc(x)
         B, H, W, C = xh.shape
-        ids = None
-        if isinstance(context, RegionalContext):
+        ids = rw = None
+        if isinstance(context, RegionalContext) and context.weights is not None:
+            # soft region weights: this level's (wts, span) (derived once per map and level, RegionalContext.level_weights)
+            rw = context.level_weights(H, W)
+            if rw[0].shape[0] != B:
+                raise ValueError(f"the region weights have {rw[0].shape[0]} batch rows, the tokens {B}")
+        elif isinstance(context, RegionalContext):
             # a prompt per region: this level's id table (derived once per map and level, RegionalContext.level_ids)
             ids = context.level_ids(H, W)
             if ids.shape[0] != B:
@@ -382,10 +451,10 @@ class SpatialTransformer(nn.Module):
         if fused:
             t, stats = ops.gemm_ln(n.view(B, H * W, C), self.proj_in.w(), self.proj_in.b32(), emit_stats=True)
             for blk in self.transformer_blocks:
-                t, stats = blk.forward_fused(t, stats, context, ids)
+                t, stats = blk.forward_fused(t, stats, context, ids, rw)
         else:
             t = ops.gemm(n.view(B, H * W, C), self.proj_in.w(), self.proj_in.b32())
             for blk in self.transformer_blocks:
-                t = blk(t, context=context, inplace=True, region_ids=ids)
+                t = blk(t, context=context, inplace=True, region_ids=ids, region_weights=rw)
         out, po = ops.gemm(t, self.proj_out.w(), self.proj_out.b32(), residual=xh.view(B, H * W, C), rows_per_batch=H * W, gn_part=True)
         return attach_gn_part(to_nchw(out.view(B, H, W, C)), po)

@@ -161,10 +161,11 @@ MAX_REGIONS = 254     # bank entries are uint8 ids and entry 0 is the unconditio
 
 class RegionSpec:
     """Regional prompts as the untiled samplers carry them in cond["regions"] until the guider builds the network's RegionalContext:
-    `contexts` = the R regions' text embeddings [1, Tk, D] (one token count), `map` = [h, w] uint8 on the latent grid, values < R."""
+    `contexts` = the R regions' text embeddings [1, Tk, D] (one token count), `map` = [h, w] uint8 on the latent grid, values < R;
+    `weights` (soft region weights, optional) = [R, h, w] float32, >= 0, summing to 1 per pixel (`map` is then their argmax)."""
 
-    def __init__(self, contexts, map):
-        self.contexts, self.map = list(contexts), map
+    def __init__(self, contexts, map, weights=None):
+        self.contexts, self.map, self.weights = list(contexts), map, weights
         self._built = None      # the RegionalContext built last and what it was built for (_regional_context): once per image
 
 
@@ -210,26 +211,98 @@ def regions_from_tiles(h, w, tile_size, tile_stride):
     return torch.from_numpy(np.argmin(d2, axis=0).astype(np.int64))      # numpy's argmin returns the first minimum
 
 
-def _regional_cond(cond, regions, x):
+def region_weights(weights, R, h, w):
+    """Soft region weights of batchify_sample -> [R, h, w] float32 on the latent grid, summing to 1 at every pixel: a float tensor or
+    array [R, h, w] is checked and divided by its per-pixel sum (in float64; an already one-hot input stays exactly one-hot).
+    ValueError: another rank or size than [R, h, w] with R the number of prompts, more than MAX_REGIONS regions, a non-finite or
+    negative value, a pixel whose weights sum to 0."""
+    if R < 1 or R > MAX_REGIONS:
+        raise ValueError(f"regional prompts take 1 .. {MAX_REGIONS} regions, got {R}")
+    if not (torch.is_tensor(weights) or isinstance(weights, np.ndarray)):
+        raise ValueError("region weights are a float tensor or array [R, h, w]")
+    t = torch.as_tensor(weights).detach().cpu()
+    if t.dim() != 3 or tuple(t.shape[1:]) != (h, w):
+        raise ValueError(f"the region weights are {tuple(t.shape)}, the latent grid {(h, w)}: expected [R, h, w]")
+    if t.shape[0] != R:
+        raise ValueError(f"region weights for {t.shape[0]} regions; there are {R} prompts")
+    if t.is_complex():
+        raise ValueError("region weights are real numbers")
+    t = t.to(torch.float64)
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError("the region weights hold non-finite values")
+    if bool((t < 0).any()):
+        raise ValueError("the region weights hold negative values")
+    tot = t.sum(0, keepdim=True)
+    if bool((tot <= 0).any()):
+        raise ValueError(f"{int((tot <= 0).sum())} latent pixels have no weight on any region")
+    return (t / tot).to(torch.float32).contiguous()
+
+
+def feather_regions(map, R, radius):
+    """Soft weights from a hard map: the (2 radius + 1)^2 box filter, with replicate padding, over the R one-hot masks of an integer map
+    [h, w] (region_map's rules) -> [R, h, w] float32.  Every window holds (2 radius + 1)^2 pixels of exactly one region each, so the
+    weights sum to 1 per pixel by construction; radius 0 returns the one-hot weights; pixels further than `radius` from every border
+    keep weight 1 on their region."""
+    radius = int(radius)
+    if radius < 0:
+        raise ValueError(f"the feather radius is {radius}: it cannot be negative")
+    m = torch.as_tensor(map)
+    if m.dim() != 2:
+        raise ValueError(f"the region map is {tuple(m.shape)}: expected [h, w]")
+    h, w = m.shape
+    m = region_map(m, R, h, w).to(torch.int64)
+    one = torch.zeros(R, h, w, dtype=torch.float64).scatter_(0, m[None], 1.0)
+    if radius == 0:
+        return one.to(torch.float32)
+    k = 2 * radius + 1
+    rows = torch.arange(-radius, h + radius).clamp_(0, h - 1)
+    cols = torch.arange(-radius, w + radius).clamp_(0, w - 1)
+    padded = one[:, rows][:, :, cols]                                       # replicate padding
+    box = torch.nn.functional.avg_pool2d(padded[None], k, stride=1, divisor_override=1)[0]     # exact integer counts
+    return (box / float(k * k)).to(torch.float32).contiguous()
+
+
+def region_weights_from_tiles(h, w, tile_size, tile_stride):
+    """The blend weights the tiled samplers give tile outputs, as soft region weights: [R, h, w] float32, region j = tile j of
+    _sliding_windows(h, w, tile_size, tile_stride); tile j's weight at a pixel is gaussian_weights(tile, tile) at the pixel's position
+    inside window j and 0 outside it, divided by the per-pixel sum over the tiles (the tiled samplers' count canvas).  The captions
+    written for per-tile prompts then fade into each other in the untiled regional call as they do under tiling."""
+    tiles = _sliding_windows(h, w, tile_size, tile_stride)
+    g = gaussian_weights(tile_size, tile_size, 1, device="cpu")[0, 0].to(torch.float64)
+    wt = torch.zeros(len(tiles), h, w, dtype=torch.float64)
+    for j, (hi, he, wi, we) in enumerate(tiles):
+        wt[j, hi:he, wi:we] = g
+    return (wt / wt.sum(0, keepdim=True)).to(torch.float32).contiguous()
+
+
+def _regional_cond(cond, regions, x, weights=None):
     """The untiled samplers' regional form: cond = the list of R per-region conditionings (the tiled samplers' local-prompt form) and
     `regions` = the [h, w] map -> region 0's conditioning (vector, control, ...: everything but the text stays global) with
-    cond["regions"] = RegionSpec for the guider's prepare_cond."""
-    if not isinstance(cond, (list, tuple)) or regions is None:
+    cond["regions"] = RegionSpec for the guider's prepare_cond.  `weights` (instead of `regions`): soft region weights [R, h, w]
+    (region_weights' rules); the spec's map is then their argmax."""
+    if regions is not None and weights is not None:
+        raise ValueError("regional prompts take `regions` (a hard map) or `region_weights` (soft weights), not both")
+    if not isinstance(cond, (list, tuple)) or (regions is None and weights is None):
         raise ValueError("regional prompts take `cond` as a list of per-region conditionings together with `regions`; "
                          "a list alone is the tiled samplers' per-tile form")
     b, _, h, w = x.shape
-    m = region_map(regions, len(cond), h, w)
+    if weights is not None:
+        weights = region_weights(weights, len(cond), h, w)
+        m = weights.argmax(0).to(torch.uint8).contiguous()
+    else:
+        m = region_map(regions, len(cond), h, w)
     ctxs = [cj["crossattn"] for cj in cond]
     if any(c.dim() != 3 or c.shape[1:] != ctxs[0].shape[1:] for c in ctxs):
         raise ValueError("every region's crossattn must have one shape [N, 77 n, D] (prepare_condition pads them to one chunk count)")
     out = dict(cond[0])
-    out["regions"] = RegionSpec([c[:1] for c in ctxs], m)
+    out["regions"] = RegionSpec([c[:1] for c in ctxs], m, weights)
     return out
 
 
 def _regional_context(spec, uc_ctx, rows_uc, rows_c, device):
     """RegionalContext of a network batch of rows_uc unconditional rows followed by rows_c conditional ones: bank = [uc; region prompts],
-    ids = 0 on the unconditional rows, 1 + r on the others."""
+    ids = 0 on the unconditional rows, 1 + r on the others.  Soft region weights (spec.weights): unconditional rows have weight 1 on
+    entry 0, conditional rows the region weights on entries 1 + r."""
     from .attention import RegionalContext
     key = (uc_ctx, uc_ctx._version, rows_uc, rows_c, str(device))
     if spec._built is not None and spec._built[0][0] is uc_ctx and spec._built[0][1:] == key[1:]:
@@ -238,7 +311,13 @@ def _regional_context(spec, uc_ctx, rows_uc, rows_c, device):
     m = spec.map.to(device)
     ids = torch.cat([torch.zeros((rows_uc,) + tuple(m.shape), dtype=torch.uint8, device=device),
                      (m + 1)[None].expand(rows_c, -1, -1)], 0).contiguous()
-    spec._built = (key, RegionalContext(bank.contiguous(), ids))
+    wts = None
+    if spec.weights is not None:
+        wr = spec.weights.to(device)
+        wts = torch.zeros((rows_uc + rows_c, 1 + wr.shape[0]) + tuple(m.shape), dtype=torch.float32, device=device)
+        wts[:rows_uc, 0] = 1.0
+        wts[rows_uc:, 1:] = wr[None]
+    spec._built = (key, RegionalContext(bank.contiguous(), ids, weights=wts))
     return spec._built[1]
 
 
@@ -428,11 +507,12 @@ class RestoreEDMSampler(BaseDiffusionSampler):
                                  float(nxt - sigma_hat), reps)
 
     def __call__(self, denoiser, x, cond, uc=None, num_steps=None, x_center=None, control_scale=1.0,
-                 use_linear_control_scale=False, control_scale_start=0.0, regions=None):
+                 use_linear_control_scale=False, control_scale_start=0.0, regions=None, region_weights=None):
         """regions (with `cond` a list of R per-region conditionings): the [h, w] map of region indices on the latent grid, or R boxes
-        (region_map) -- every text cross-attention then restricts each token to its region's prompt, in ONE untiled network call."""
-        if regions is not None or isinstance(cond, (list, tuple)):
-            cond = _regional_cond(cond, regions, x)
+        (region_map) -- every text cross-attention then restricts each token to its region's prompt, in ONE untiled network call.
+        region_weights (instead): soft weights [R, h, w] -- every text cross-attention outputs the weighted sum over the regions."""
+        if regions is not None or region_weights is not None or isinstance(cond, (list, tuple)):
+            cond = _regional_cond(cond, regions, x, region_weights)
         x, s_in, sigmas, num_sigmas, cond, uc, sf = self.prepare_sampling_loop(x, cond, uc, num_steps)
         cond_cat = self.guider.prepare_cond(cond, uc)            # constant over the loop: concat once
         inject = self.__dict__.pop("injected_step_noises", None)  # parity runs: the churn noise of every step, given
@@ -631,8 +711,8 @@ class TiledRestoreEDMSampler(_TileGroups, RestoreEDMSampler):
         self.tile_weights = None
 
     def __call__(self, denoiser, x, cond, uc=None, num_steps=None, x_center=None, control_scale=1.0,
-                 use_linear_control_scale=False, control_scale_start=0.0, regions=None):
-        if regions is not None:
+                 use_linear_control_scale=False, control_scale_start=0.0, regions=None, region_weights=None):
+        if regions is not None or region_weights is not None:
             raise ValueError("the tiled samplers take per-tile prompts (their windows are the regions), not `regions`")
         use_local_prompt = isinstance(cond, list)
         self.__dict__["_rep_cache"] = {}   # the repeated-conditioning cache is per call (`static` below is rebuilt every call)
@@ -943,10 +1023,10 @@ class RestoreDPMPP2MSampler(BaseDiffusionSampler):
                 net.end_schedule()
         return x
 
-    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, control_scale=1.0, regions=None, **kwargs):
-        """regions: as on RestoreEDMSampler."""
-        if regions is not None or isinstance(cond, (list, tuple)):
-            cond = _regional_cond(cond, regions, x)
+    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, control_scale=1.0, regions=None, region_weights=None, **kwargs):
+        """regions / region_weights: as on RestoreEDMSampler."""
+        if regions is not None or region_weights is not None or isinstance(cond, (list, tuple)):
+            cond = _regional_cond(cond, regions, x, region_weights)
         x, s_in, sigmas, num_sigmas, cond, uc, sf, smin, smax = self._karras(x, cond, uc, num_steps)
         cond_cat = self.guider.prepare_cond(cond, uc)
         noise_sampler = self.noise_sampler_cls(x, smin, smax)
@@ -972,9 +1052,9 @@ class TiledRestoreDPMPP2MSampler(_TileGroups, RestoreDPMPP2MSampler):
         super().__init__(*args, **kwargs)
         self._init_tiling(tile_size, tile_stride, tile_batch, tile_parallel, process_group, tile_batch_local_prompts)
 
-    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, control_scale=1.0, regions=None, **kwargs):
+    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, control_scale=1.0, regions=None, region_weights=None, **kwargs):
         import torch.distributed as dist
-        if regions is not None:
+        if regions is not None or region_weights is not None:
             raise ValueError("the tiled samplers take per-tile prompts (their windows are the regions), not `regions`")
         use_local_prompt = isinstance(cond, list)
         self.__dict__["_rep_cache"] = {}   # per call, like TiledRestoreEDMSampler's

@@ -298,14 +298,20 @@ class ControlWrapper(nn.Module):
         """The persistent RegionalContext serving calls shaped like `reg`, holding reg's bank and map (loaded in place; nothing happens
         while reg is unchanged, i.e. on every step of an image after the first).  The text K / V^T of the bank (per layer,
         CrossAttention._context_kv(..., "regions")) and the id tables of the levels hang off its buffers, so one graph per shape serves
-        every image, every map and every region count up to the capacity; a bank that outgrows it gets a larger slot (and graph)."""
+        every image, every map and every region count up to the capacity; a bank that outgrows it gets a larger slot (and graph).
+        Soft region weights (reg.weights) are part of the key: hard and soft calls of one shape hold separate buffers and separate
+        captured graphs, and a soft slot's weights [B, cap, h, w] and level tables are refreshed in place like the ids."""
         from .attention import RegionalContext
         step = self.REGION_BANK_STEP
-        key = (tuple(reg.ids.shape), tuple(reg.bank.shape[1:]), reg.bank.dtype, reg.bank.device, Wt.cdt())
+        key = (tuple(reg.ids.shape), tuple(reg.bank.shape[1:]), reg.bank.dtype, reg.bank.device, Wt.cdt()) + (
+            ("soft",) if reg.weights is not None else ())
         slot = self._region_slots.get(key)
         if slot is None or slot.cap < reg.n:
             cap = min(255, (reg.n + step - 1) // step * step)
-            slot = RegionalContext(reg.bank.new_zeros((cap,) + tuple(reg.bank.shape[1:])), torch.zeros_like(reg.ids), n=reg.n)
+            wts = None
+            if reg.weights is not None:
+                wts = reg.weights.new_zeros((reg.weights.shape[0], cap) + tuple(reg.weights.shape[2:]))
+            slot = RegionalContext(reg.bank.new_zeros((cap,) + tuple(reg.bank.shape[1:])), torch.zeros_like(reg.ids), n=reg.n, weights=wts)
             self._region_slots[key] = slot
         slot.load(reg)
         return slot

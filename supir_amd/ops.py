@@ -1397,6 +1397,74 @@ def xattn_q_regions(x, wq, bias, k_bank, vt_bank, ids, B, H, T, Tk, *, ln=None, 
     return out
 
 
+def xattn_q_regions_soft_supported(B, T, C, H, Tk, NR):
+    """Shape predicate of supir_xattn_q_d64_regions_soft (csrc/xattn.hip): the rules of xattn_q_regions_supported."""
+    return xattn_q_regions_supported(B, T, C, H, Tk, NR)
+
+
+def attn_regions_soft(q, k_bank, vt_bank, wts, B, H, T, Tk, entries=None):
+    """The plain form of soft regional text attention: q [B,T,H*64], banks k [NR,Tk,H*64] / vt [NR,H*64,Tpad], wts [B,NR,T] float32
+    (>= 0, summing to 1 over the entries) -> [B,T,H*64] = sum_e wts[b,e,t] * (token (b,t)'s attention to the Tk keys of entry e).  The
+    existing attention runs once per entry (`entries`: default every one of the bank, as in attn_regions and for the same reason) over
+    ALL tokens; the weighted sum is formed in fp32 and cast once.  Any element type; nobody tunes it."""
+    NR = k_bank.shape[0]
+    w = wts.reshape(B, NR, T, 1)
+    acc = None
+    for e in (range(NR) if entries is None else entries):
+        ke = k_bank[e:e + 1].expand(B, -1, -1).contiguous()
+        ve = vt_bank[e:e + 1].expand(B, -1, -1).contiguous()
+        a = flash_attn(q, ke, ve, B, H, T, Tk).float() * w[:, e]
+        acc = a if acc is None else acc.add_(a)
+    return acc.to(q.dtype)
+
+
+def xattn_q_regions_soft(x, wq, bias, k_bank, vt_bank, wts, span, B, H, T, Tk, *, ln=None, colsum=None, ln_eps=1e-5, out=None, entries=None):
+    """xattn_q_regions with soft region weights: wts [B,NR,T] (float32, >= 0, summing to 1 over the NR bank entries) gives every token
+    a weight per entry and span [B,T/128,2] (uint8: first and last entry with a non-zero weight per 128-token block,
+    attention.level_region_weights derives both) bounds each workgroup's walk; the output is sum_e wts[b,e,t] softmax(q K_e^T / 8) V_e,
+    one launch of supir_xattn_q_d64_regions_soft.  Shapes the kernel refuses (span is None there), fp32 operands and the switch
+    SUPIR_FUSED_XATTN=0 take the projection and attn_regions_soft instead."""
+    DT = x.dtype
+    M, C, ldx = _rows_ld(x)
+    NR = k_bank.shape[0]
+    assert wts.dtype == torch.float32 and wts.is_contiguous() and tuple(wts.shape) == (B, NR, T) and M == B * T
+    assert k_bank.shape[1] == Tk and k_bank.dtype == DT and vt_bank.dtype == DT
+    if DT not in HALF_TYPES or span is None or not xattn_q_regions_soft_supported(B, T, C, H, Tk, NR):
+        if ln is not None:
+            q = gemm_ln(x, wq, bias, ln=ln, colsum=colsum, ln_eps=ln_eps)
+        else:
+            q = gemm(x, wq, bias)
+        return attn_regions_soft(q.view(B, T, H * 64), k_bank, vt_bank, wts, B, H, T, Tk, entries=entries)
+    lib = _lib.load(DT)
+    _check_dev(x, wq, k_bank, vt_bank, wts, span)
+    assert span.dtype == torch.uint8 and span.is_contiguous() and tuple(span.shape) == (B, T // 128, 2)
+    assert wq.shape == (H * 64, C) and wq.is_contiguous() and wq.dtype == DT
+    assert k_bank.stride(-1) == 1 and vt_bank.is_contiguous() and vt_bank.shape[1] == H * 64
+    ldk, ldvt = k_bank.stride(-2), vt_bank.shape[-1]
+    assert k_bank.stride(0) == Tk * ldk
+    if out is None:
+        out = torch.empty(B, T, H * 64, dtype=DT, device=x.device)
+    assert out.dtype == DT
+    _, _, ldo = _rows_ld(out)
+    ln_p, ln_ld, ln_slots = 0, 0, 0
+    if ln is not None:
+        ln_p, ln_ld, ln_slots = ln.buf.data_ptr(), ln.ld, ln.slots
+        assert colsum is not None and colsum.numel() == H * 64
+
+    def launch(t, outp=None, hints=None):
+        return lib.supir_xattn_q_d64_regions_soft(x.data_ptr(), wq.data_ptr(), _p(bias), k_bank.data_ptr(), vt_bank.data_ptr(),
+                                                  wts.data_ptr(), span.data_ptr(), NR, (out if outp is None else outp).data_ptr(), B, H, T,
+                                                  Tk, C, ldx, ldk, ldvt, ldo, ln_p, ln_ld, ln_slots, _p(colsum), ln_eps, 0.125,
+                                                  None if hints is None else _ct.byref(hints), _stream())
+
+    N = H * 64
+    _issue(_Launch(None, lib, "supir_xattn_q_d64_regions_soft", launch, w=wq, out=out,
+                   trace=("xattn_q_regions_soft", 2.0 * M * N * C + 4.0 * M * N * Tk * NR,
+                          2.0 * (M * C + N * C + M * N + 2 * NR * Tk * N) + 4.0 * M * NR, dict(B=B, H=H, T=T, Tk=Tk, C=C, NR=NR)),
+                   keep=(x, wq, bias, k_bank, vt_bank, wts, span, out, ln.buf if ln is not None else None, colsum)))
+    return out
+
+
 # VAE mid-block attention (one head, dim 512): supir_flash_attn_d512 never forms the score matrix; the materialised form (GEMM -> fp32
 # scores [T, T] -> softmax_rows -> GEMM) moves ~3 GB per call at T = 16 384 but runs on the tuned GEMM tiles.  Until round 4 the flash
 # kernel had B * T / 128 workgroups of one wave per SIMD and lost below 16 384 tokens (T = 4096: 391 us vs 93 us materialised,
